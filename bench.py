@@ -11,6 +11,12 @@ windows per GPU fills the 256 CUs).
 
   python bench.py [--gpus N --steps K --warmup W --windows 256 --lm-iters 10]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the
+roofline of the timed steps).  --dump-outputs DIR writes what the last timed step computed for every
+window as DIR/<name>.npy.  --full adds every other leg to the line: the sustained run, the single
+window, the CPU oracle baselines, config 4 strong scaling and its 32-window shard, config 2, the
+tracker, global BA, IMU, triangulation and resize legs (the --no-* options drop single legs of it).
 """
 import argparse
 import ctypes as C
@@ -192,12 +198,42 @@ def reduce_max(x, dist, device):
     return float(t.item())
 
 
-def make_shard(vio, synth, rank, windows, lm_iters):
-    probs = []
-    for seed in shard_seeds(synth.SEED, rank, windows):
-        w = synth.config3(seed)
-        probs.append(vio.BaProblem(w, variant=vio.VIO_BA_VI, max_iterations=lm_iters, fixed_iterations=1))
-    return probs
+def _config3_window(seed):
+    return importlib.import_module("360_visual_inertial_odometry_amd.synth").config3(seed)
+
+
+def shard_windows(synth, rank, windows):
+    """The shard's config-3 windows (synth.config3 of every seed of shard_seeds: each window is a function
+    of its seed alone, ~0.1 s of numpy), generated over a pool of forked host processes.  Call it before
+    this process opens the GPU."""
+    import multiprocessing
+    seeds = shard_seeds(synth.SEED, rank, windows)
+    n = min(16, cpu_threads_available(), len(seeds))
+    if n <= 1:
+        return [synth.config3(s) for s in seeds]
+    with multiprocessing.get_context("fork").Pool(n) as pool:
+        return pool.map(_config3_window, seeds, chunksize=-(-len(seeds) // (4 * n)))
+
+
+def make_shard(vio, shard, lm_iters):
+    return [vio.BaProblem(w, variant=vio.VIO_BA_VI, max_iterations=lm_iters, fixed_iterations=1) for w in shard]
+
+
+DUMP_ARRAYS = ("T_wb", "lm_xyz", "vel", "bg", "ba", "obs_chi2", "obs_outlier", "lm_bad")
+DUMP_SCALARS = ("success", "termination", "iterations", "num_successful_steps", "num_unsuccessful_steps",
+                "num_inliers", "num_outliers", "num_bad_lm", "initial_cost", "final_cost", "fixed_cost")
+
+
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: the shard's results of the last timed step (BaBatch.download(): what a caller of the
+    timed path receives for every window) as <path>/<name>.npy, float64, the windows stacked along axis 0
+    (<name>_rank<r>.npy for the shard of rank r in a multi-rank run).  ~60 kB per config-3 window."""
+    os.makedirs(path, exist_ok=True)
+    tail = "" if world == 1 else f"_rank{rank}"
+    for name in DUMP_ARRAYS:
+        np.save(os.path.join(path, f"{name}{tail}.npy"), np.stack([np.asarray(r[name], np.float64) for r in res]))
+    for name in DUMP_SCALARS:
+        np.save(os.path.join(path, f"{name}{tail}.npy"), np.array([r[name] for r in res], np.float64))
 
 
 def config4_strong(vio, synth, ctx, dist, rank, world, steps, warmup, lm_iters, total=256):
@@ -743,6 +779,72 @@ def resize_bench(vio, ctx, steps, want_cpu):
     }
 
 
+def full_legs(vio, synth, ctx, args, world, probs, elapsed, sustained, c4):
+    """--full, rank 0: every leg of the line beside the headline (the --no-* options drop single ones)."""
+    want_cpu = not args.no_cpu_baseline and world == 1
+    # single-window latency (config 3 exactly, one window per launch) for the >=50x CPU target
+    one = vio.BaBatch(ctx, probs[:1])
+    single_route, single_wg = one.route()
+    for _ in range(3):
+        one.run()
+    one.sync()
+    one.kernel_ms()
+    t1 = time.perf_counter()
+    n1 = 100
+    for _ in range(n1):
+        one.run()
+    one.sync()
+    single_wall = (time.perf_counter() - t1) / n1
+    single_kms, _ = one.kernel_ms()
+    one.close()
+    # the same window through vio_ba_solve: host problem in, host result out (upload + solve +
+    # download per call, SURVEY §8d's single-window definition)
+    single_xfer_wall, single_py_wall = time_solve_call(vio, ctx, probs[:1], n1)
+    cpu = cpu_baseline(vio, synth, args.lm_iters, args.cpu_seconds) if want_cpu else None
+    gba = None if args.no_global else global_ba_bench(vio, synth, ctx, args.lm_iters, want_cpu)
+    c2 = None if args.no_config2 else config2_bench(vio, synth, ctx, args.lm_iters, args.cpu_seconds, want_cpu)
+    shard = shard_bench(vio, synth, ctx, args.lm_iters)
+    klt = None if args.no_klt else klt_bench(vio, synth, ctx, args.klt_steps, 3, args.cpu_seconds, want_cpu)
+    imu = None if args.no_imu else imu_bench(vio, ctx, 20, min(args.cpu_seconds, 3.0), want_cpu)
+    tri = None if args.no_tri else tri_bench(vio, ctx, 20, want_cpu)
+    rsz = None if args.no_resize else resize_bench(vio, ctx, 20, want_cpu)
+    single_ips = args.lm_iters / single_wall
+    return {
+        "single_window": {
+            "config": "config 3 (one window per launch)",
+            "iters_per_s_wall": single_ips,
+            "iters_per_s_with_transfer": args.lm_iters / single_xfer_wall,
+            "ms_per_solve_call": single_xfer_wall * 1e3,
+            "iters_per_s_python_call": args.lm_iters / single_py_wall,
+            "kernel_ms": single_kms,
+            "route": single_route,
+            "workgroups": single_wg,
+            "vs_cpu_1t": (single_ips / cpu["single_window_threads"]["1"]) if cpu else None,
+            "vs_cpu_4t": (single_ips / cpu["single_window_threads"]["4"]) if cpu else None,
+            "vs_cpu_4t_with_transfer": (args.lm_iters / single_xfer_wall / cpu["single_window_threads"]["4"])
+            if cpu else None,
+            "note": "resident = BaBatch re-run on device-resident inputs; with_transfer = one "
+                    "vio_ba_solve_batched C-ABI call per solve on host buffers (pack + one pinned upload + solve "
+                    "+ one pinned download + scatter; the call's structs built once, as a C++ host holds its "
+                    "windows); python_call = Context.ba_solve (ctypes marshalling and result dicts included); "
+                    "CPU = the oracle on one window at 1 / 4 threads inside the solve",
+        },
+        "sustained": sustained,
+        "cpu_baseline": cpu,
+        "config4_strong": c4,
+        "config4_shard32": dict(shard, projected_8gpu_speedup=(elapsed / args.steps * 1e3) / shard["ms_per_step"]
+                                if args.windows == 256 else None,
+                                note="the 8-GPU strong-scaling shard (256 / 8 windows) on this GPU; projection = "
+                                     "this run's 256-window step / the 32-window step (the all-gather is ~30 us)"),
+        "config2": c2,
+        "erp_klt": klt,
+        "global_ba": gba,
+        "imu_preint": imu,
+        "triangulation": tri,
+        "frame_resize": rsz,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -760,11 +862,18 @@ def main():
     ap.add_argument("--no-resize", action="store_true")
     ap.add_argument("--no-config4", action="store_true")
     ap.add_argument("--no-config2", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (sustained run, single window, CPU baselines, "
+                         "config 4 / 2, tracker, global BA, IMU, triangulation, resize)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write every window's results of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    synth = importlib.import_module("360_visual_inertial_odometry_amd.synth")
+    shard = shard_windows(synth, rank, args.windows)  # host processes: before torch and the GPU runtime load
     import torch
     dist = None
     if world > 1:
@@ -772,10 +881,9 @@ def main():
         torch.cuda.set_device(local_rank)
         dist.init_process_group("nccl")
     vio = importlib.import_module("360_visual_inertial_odometry_amd")
-    synth = importlib.import_module("360_visual_inertial_odometry_amd.synth")
 
     ctx = vio.Context(local_rank)
-    probs = make_shard(vio, synth, rank, args.windows, args.lm_iters)
+    probs = make_shard(vio, shard, args.lm_iters)
     flops_iter = sum(ba_flops_per_iter(p) for p in probs)
     batch = vio.BaBatch(ctx, probs)
     for _ in range(args.warmup):
@@ -798,10 +906,16 @@ def main():
     kms, kcount = batch.kernel_ms()
     elapsed = reduce_max(elapsed, dist, f"cuda:{local_rank}")
     head_route, _ = batch.route()
-    # a sustained run of >= 200 steps beside the K timed steps (clock ramp / launch jitter check of a short
-    # timed region); reported, never the value
+    # sanity: every window actually ran its iterations (every run solves from the resident inputs again, so
+    # this is what the last timed step computed)
+    res = batch.download()
+    assert all(r["iterations"] == args.lm_iters + 1 and r["final_cost"] < r["initial_cost"] for r in res)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
+    # --full: a sustained run of >= 200 steps beside the K timed steps (clock ramp / launch jitter check of a
+    # short timed region); reported, never the value
     sustained = None
-    if args.steps < 200:
+    if args.full and args.steps < 200:
         barrier()
         t0 = time.perf_counter()
         for _ in range(200):
@@ -812,17 +926,15 @@ def main():
         batch.kernel_ms()
         sustained = {"steps": 200, "ms_per_step": s_el / 200 * 1e3,
                      "value": world * args.windows * args.lm_iters * 200 / s_el}
-    # sanity: every window actually ran its iterations
-    res = batch.download()
-    assert all(r["iterations"] == args.lm_iters + 1 and r["final_cost"] < r["initial_cost"] for r in res)
     batch.close()
 
     total_iters = world * args.windows * args.lm_iters * args.steps
     value = total_iters / elapsed
     achieved = flops_iter * args.lm_iters / (kms * 1e-3)
 
-    c4 = None if args.no_config4 else config4_strong(vio, synth, ctx, dist, rank, world, args.steps, args.warmup,
-                                                       args.lm_iters)
+    c4 = None
+    if args.full and not args.no_config4:
+        c4 = config4_strong(vio, synth, ctx, dist, rank, world, args.steps, args.warmup, args.lm_iters)
     mix, mix_src = sq_mix()
     mix_note = ""
     if mix:
@@ -834,37 +946,6 @@ def main():
                     f"bound), ph_schur {_busy('ph_schur_kernel'):.3f}, ph_solve {_busy('ph_solve_kernel'):.3f}")
     out = None
     if rank == 0:
-        # single-window latency (config 3 exactly, one window per launch) for the >=50x CPU target
-        one = vio.BaBatch(ctx, probs[:1])
-        single_route, single_wg = one.route()
-        for _ in range(3):
-            one.run()
-        one.sync()
-        one.kernel_ms()
-        t1 = time.perf_counter()
-        n1 = 100
-        for _ in range(n1):
-            one.run()
-        one.sync()
-        single_wall = (time.perf_counter() - t1) / n1
-        single_kms, _ = one.kernel_ms()
-        one.close()
-        # the same window through vio_ba_solve: host problem in, host result out (upload + solve +
-        # download per call, SURVEY §8d's single-window definition)
-        single_xfer_wall, single_py_wall = time_solve_call(vio, ctx, probs[:1], n1)
-        cpu = None if args.no_cpu_baseline or world > 1 else cpu_baseline(vio, synth, args.lm_iters, args.cpu_seconds)
-        gba = None if args.no_global else global_ba_bench(vio, synth, ctx, args.lm_iters,
-                                                           not args.no_cpu_baseline and world == 1)
-        c2 = None if args.no_config2 else config2_bench(vio, synth, ctx, args.lm_iters, args.cpu_seconds,
-                                                        not args.no_cpu_baseline and world == 1)
-        shard = shard_bench(vio, synth, ctx, args.lm_iters)
-        klt = None if args.no_klt else klt_bench(vio, synth, ctx, args.klt_steps, 3, args.cpu_seconds,
-                                                 not args.no_cpu_baseline and world == 1)
-        imu = None if args.no_imu else imu_bench(vio, ctx, 20, min(args.cpu_seconds, 3.0),
-                                                 not args.no_cpu_baseline and world == 1)
-        tri = None if args.no_tri else tri_bench(vio, ctx, 20, not args.no_cpu_baseline and world == 1)
-        rsz = None if args.no_resize else resize_bench(vio, ctx, 20, not args.no_cpu_baseline and world == 1)
-        single_ips = args.lm_iters / single_wall
         out = {
             "metric": "sliding-window BA iters/sec (10KF x 500pts)",
             "value": value,
@@ -903,39 +984,9 @@ def main():
                 "sq_mix": mix,
                 "sq_mix_source": mix_src,
             },
-            "single_window": {
-                "config": "config 3 (one window per launch)",
-                "iters_per_s_wall": single_ips,
-                "iters_per_s_with_transfer": args.lm_iters / single_xfer_wall,
-                "ms_per_solve_call": single_xfer_wall * 1e3,
-                "iters_per_s_python_call": args.lm_iters / single_py_wall,
-                "kernel_ms": single_kms,
-                "route": single_route,
-                "workgroups": single_wg,
-                "vs_cpu_1t": (single_ips / cpu["single_window_threads"]["1"]) if cpu else None,
-                "vs_cpu_4t": (single_ips / cpu["single_window_threads"]["4"]) if cpu else None,
-                "vs_cpu_4t_with_transfer": (args.lm_iters / single_xfer_wall / cpu["single_window_threads"]["4"])
-                if cpu else None,
-                "note": "resident = BaBatch re-run on device-resident inputs; with_transfer = one "
-                        "vio_ba_solve_batched C-ABI call per solve on host buffers (pack + one pinned upload + solve "
-                        "+ one pinned download + scatter; the call's structs built once, as a C++ host holds its "
-                        "windows); python_call = Context.ba_solve (ctypes marshalling and result dicts included); "
-                        "CPU = the oracle on one window at 1 / 4 threads inside the solve",
-            },
-            "sustained": sustained,
-            "cpu_baseline": cpu,
-            "config4_strong": c4,
-            "config4_shard32": dict(shard, projected_8gpu_speedup=(elapsed / args.steps * 1e3) / shard["ms_per_step"]
-                                    if args.windows == 256 else None,
-                                    note="the 8-GPU strong-scaling shard (256 / 8 windows) on this GPU; projection = "
-                                         "this run's 256-window step / the 32-window step (the all-gather is ~30 us)"),
-            "config2": c2,
-            "erp_klt": klt,
-            "global_ba": gba,
-            "imu_preint": imu,
-            "triangulation": tri,
-            "frame_resize": rsz,
         }
+        if args.full:
+            out.update(full_legs(vio, synth, ctx, args, world, probs, elapsed, sustained, c4))
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -1,4 +1,4 @@
-"""Summary of a bench.py JSON line (the last '{' line of a log): headline, legs, CPU baselines."""
+"""Summary of a `bench.py --full` JSON line (the last '{' line of a log): headline, legs, CPU baselines."""
 import json
 import sys
 

@@ -36,6 +36,7 @@ EXPORTS = [
     "vio_triangulate", "vio_triangulate_device", "vio_triangulate_kernel_ms",
     "vio_load_camera_timestamps", "vio_load_imu_csv", "erp_resize_area", "erp_resize_area_device",
     "erp_resize_area_kernel_ms", "erp_tracker_upload_resized",
+    "erp_resize_area_any", "erp_resize_area_any_device", "erp_resize_area_tab", "erp_frontend_track_resized",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -117,6 +118,10 @@ def lib():
     L.erp_resize_area_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]
     L.erp_resize_area_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.erp_tracker_upload_resized.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+    L.erp_resize_area_any.argtypes = L.erp_resize_area.argtypes
+    L.erp_resize_area_any_device.argtypes = L.erp_resize_area_device.argtypes
+    L.erp_resize_area_tab.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.erp_frontend_track_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -320,6 +325,32 @@ class Context:
     def resize_area_device(self, src_ptr, W, H, stride, n_frames, dst_ptr, dW, dH, dst_stride):
         self.check(lib().erp_resize_area_device(self.h, src_ptr, W, H, stride, n_frames, dst_ptr, dW, dH, dst_stride),
                    "erp_resize_area_device")
+
+    def resize_area_any(self, img, dW, dH):
+        """cv::resize(..., INTER_AREA) of a u8 frame to any (dW, dH) no larger than the frame: integer
+        factors as resize_area, every other size through OpenCV's general area path."""
+        a = _u8img(img)
+        H, W = a.shape
+        out = np.zeros((dH, dW), np.uint8)
+        self.check(lib().erp_resize_area_any(self.h, _p(a), W, H, a.strides[0], _p(out), dW, dH, dW),
+                   "erp_resize_area_any")
+        return out
+
+    def resize_area_any_device(self, src_ptr, W, H, stride, n_frames, dst_ptr, dW, dH, dst_stride):
+        self.check(lib().erp_resize_area_any_device(self.h, src_ptr, W, H, stride, n_frames, dst_ptr, dW, dH,
+                                                    dst_stride), "erp_resize_area_any_device")
+
+    @staticmethod
+    def resize_area_tab(ssize, dsize):
+        """erp_resize_area_tab (host): one axis' taps of the general path -> (di int32, si int32, alpha f32)."""
+        n = C.c_int()
+        rc = lib().erp_resize_area_tab(int(ssize), int(dsize), None, None, None, 0, C.byref(n))
+        if rc:
+            raise VioError(f"erp_resize_area_tab({ssize}, {dsize}) failed ({rc})")
+        di, si = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.int32)
+        al = np.zeros(max(n.value, 1), np.float32)
+        lib().erp_resize_area_tab(int(ssize), int(dsize), _p(di), _p(si), _p(al), n.value, C.byref(n))
+        return di[:n.value], si[:n.value], al[:n.value]
 
     def resize_kernel_ms(self):
         ms = C.c_double()
@@ -601,6 +632,19 @@ class Frontend:
         img = _u8img(img)
         n = C.c_int()
         self.ctx.check(lib().erp_frontend_track(self.h, _p(img), img.shape[1], C.byref(n)), "erp_frontend_track")
+        return self._features(n.value)
+
+    def track_resized(self, img):
+        """erp_frontend_track_resized: track on a camera-resolution frame, INTER_AREA-resized on the device."""
+        img = _u8img(img)
+        H, W = img.shape
+        n = C.c_int()
+        self.ctx.check(lib().erp_frontend_track_resized(self.h, _p(img), W, H, img.strides[0], C.byref(n)),
+                       "erp_frontend_track_resized")
+        return self._features(n.value)
+
+    def _features(self, count):
+        n = C.c_int(count)
         ids = np.zeros(n.value, np.int32)
         xy = np.zeros((n.value, 2), np.float32)
         tc = np.zeros(n.value, np.int32)

@@ -25,6 +25,9 @@ struct vio_ctx {
     hipEvent_t tri_ev[2] = {nullptr, nullptr};
     // INTER_AREA resize kernel timing (created on first use)
     hipEvent_t rsz_ev[2] = {nullptr, nullptr};
+    // (W, dW, H, dH) of the general INTER_AREA tap tables now in kSlotResizeTabX / kSlotResizeTabY
+    int rsz_tab_key[4] = {0, 0, 0, 0};
+    int rsz_max_x_taps = 0;  // the largest tap count of a column of those tables
     // monocular initialisation kernels timing (created on first use)
     hipEvent_t init_ev[2] = {nullptr, nullptr};
     // window-BA execution route (vio_ctx_set_ba_route)
@@ -59,6 +62,8 @@ enum { kSlotLie = 18 };
 enum { kSlotBaSolve = 19 };
 // the global BA solves' arena (inputs, outputs, the dense reduced system and the rest of the state)
 enum { kSlotGbaSolve = 20 };
+// erp_resize_area_any: the per-output-column / per-output-row tap tables of the general path
+enum { kSlotResizeTabX = 21, kSlotResizeTabY = 22 };
 // pinned host slots: the one-shot solves' input image and every BA download's outputs image
 enum { kHostSlotBaIn = 0, kHostSlotBaOut = 1, kHostSlotGba = 2 };
 

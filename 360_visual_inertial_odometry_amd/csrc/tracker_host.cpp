@@ -568,7 +568,7 @@ int erp_tracker_upload_resized(erp_tracker* t, int slot, const uint8_t* img, int
         return VIO_ENOMEM;
     }
     VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    return erp_resize_area_device(ctx, d_src, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
+    return erp_resize_area_any_device(ctx, d_src, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
 }
 
 int erp_tracker_device_frame(erp_tracker* t, int slot, uint8_t** dev_ptr, int* pitch) {
@@ -1052,14 +1052,13 @@ void erp_frontend_destroy(erp_frontend* f) {
     delete f;
 }
 
-int erp_frontend_track(erp_frontend* f, const uint8_t* img, int stride, int* n_features) {
-    if (!f || !img) return VIO_EINVAL;
+// TrackFeatures on the frame now in slot 1
+static int frontend_track_slot1(erp_frontend* f, int* n_features) {
     erp_tracker* t = f->t;
     vio_ctx* ctx = t->ctx;
     VIO_DEVICE(ctx);
     hipStream_t st = ctx->stream;
     int rc;
-    if ((rc = upload_frame(t, 1, img, stride))) return rc;
     const erp_frontend_params& P = f->p;
     if (f->frame == 0 || f->feats.empty()) {
         // first frame (or nothing to track): detect only (:68-97)
@@ -1137,6 +1136,20 @@ int erp_frontend_track(erp_frontend* f, const uint8_t* img, int stride, int* n_f
     f->frame++;
     if (n_features) *n_features = (int)f->feats.size();
     return VIO_OK;
+}
+
+int erp_frontend_track(erp_frontend* f, const uint8_t* img, int stride, int* n_features) {
+    if (!f || !img) return VIO_EINVAL;
+    int rc;
+    if ((rc = upload_frame(f->t, 1, img, stride))) return rc;
+    return frontend_track_slot1(f, n_features);
+}
+
+int erp_frontend_track_resized(erp_frontend* f, const uint8_t* img, int W, int H, int stride, int* n_features) {
+    if (!f || !img) return VIO_EINVAL;
+    int rc;
+    if ((rc = erp_tracker_upload_resized(f->t, 1, img, W, H, stride))) return rc;
+    return frontend_track_slot1(f, n_features);
 }
 
 int erp_frontend_features(erp_frontend* f, int32_t* ids, float* xy, int32_t* track_count, int32_t* age, int cap) {

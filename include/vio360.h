@@ -427,8 +427,8 @@ int erp_tracker_create(vio_ctx* ctx, int W, int H, int max_points, int max_corne
 int erp_tracker_upload(erp_tracker* t, int slot, const uint8_t* img, int stride);
 int erp_tracker_device_frame(erp_tracker* t, int slot, uint8_t** dev_ptr, int* pitch);
 /* the demo's frame path (app/main.cpp:199-204): upload a W x H u8 camera frame and resize it on the
-   device with INTER_AREA (erp_resize_area) into slot's tracker resolution; integer factors only
-   (VIO_ENOSYS otherwise), a frame already at tracker resolution is uploaded as is */
+   device with INTER_AREA (erp_resize_area_any_device) into slot's tracker resolution; any downscale
+   (enlarging is VIO_ENOSYS), a frame already at tracker resolution is uploaded as is */
 int erp_tracker_upload_resized(erp_tracker* t, int slot, const uint8_t* img, int W, int H, int stride);
 /* swap slots 0 and 1 (the current frame becomes the previous one, m_prev_image = current) */
 int erp_tracker_swap(erp_tracker* t);
@@ -486,6 +486,9 @@ typedef struct {
 int erp_frontend_create(vio_ctx* ctx, int W, int H, const erp_frontend_params* p, erp_frontend** out);
 /* process the next frame (u8 W x H); *n_features = features of this frame after the call */
 int erp_frontend_track(erp_frontend* f, const uint8_t* img, int stride, int* n_features);
+/* the same on a camera-resolution frame (u8 W x H), resized on the device to the front end's size as
+   erp_tracker_upload_resized does */
+int erp_frontend_track_resized(erp_frontend* f, const uint8_t* img, int W, int H, int stride, int* n_features);
 /* current frame's features in Frame order: id, pixel, track count, age (any pointer may be NULL) */
 int erp_frontend_features(erp_frontend* f, int32_t* ids, float* xy, int32_t* track_count, int32_t* age, int cap);
 /* GetTrackingStats (FeatureTracker.h): features after tracking, new detections of the last frame */
@@ -617,6 +620,21 @@ int erp_resize_area_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int s
                            int dW, int dH, int dst_stride);
 /* device time (ms) of the last resize kernel on this context (waits for it) */
 int erp_resize_area_kernel_ms(vio_ctx* ctx, double* ms);
+/* cv::resize(..., INTER_AREA) to any size dW <= W, dH <= H (4096x2048 or 5376x2688 -> 960x480, ...).
+   Integer factors on both axes run erp_resize_area's kernels (bitwise the same result); every other size runs
+   OpenCV's general area path: per-axis tap tables (computeResizeAreaTab, built on the host in double and cached
+   on the context per (W, dW, H, dH)), f32 accumulation in tap order, round half to even.  Enlarging on either
+   axis is VIO_ENOSYS.  Blocking; host buffers. */
+int erp_resize_area_any(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, uint8_t* dst, int dW, int dH,
+                        int dst_stride);
+/* the same for n_frames DEVICE frames (laid out as for erp_resize_area_device), async on the context stream
+   (a call with sizes other than the previous general call's first uploads their tap tables and waits for that) */
+int erp_resize_area_any_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, int n_frames,
+                               uint8_t* dst, int dW, int dH, int dst_stride);
+/* host only: one axis' tap table of the general path (ssize -> dsize <= ssize), taps ordered by output index
+   and then by source index: output index di[i] += alpha[i] * source index si[i].  Writes min(cap, count) taps,
+   *n = count (call with cap = 0 to size the buffers). */
+int erp_resize_area_tab(int ssize, int dsize, int32_t* di, int32_t* si, float* alpha, int cap, int* n);
 
 
 /* ------------------------------------------------------------------------------------------ */

@@ -19,6 +19,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIO360_LIB") or os.path.join(_HERE, "libvio360.so")
 _lib = None
 
+# pixel formats, luma rules and execution routes of the colour ingest (include/vio360.h)
+VIO_PIX_GRAY8, VIO_PIX_BGR8, VIO_PIX_RGB8, VIO_PIX_BGRA8, VIO_PIX_RGBA8, VIO_PIX_YUYV, VIO_PIX_UYVY = range(7)
+VIO_LUMA_CVTCOLOR, VIO_LUMA_IMREAD = 0, 1
+VIO_INGEST_ROUTE_AUTO, VIO_INGEST_ROUTE_FUSED, VIO_INGEST_ROUTE_TWO_PASS, VIO_INGEST_ROUTE_FUSED_BYTES = range(4)
+
 EXPORTS = [
     "vio_abi_version", "vio_ctx_create", "vio_ctx_destroy", "vio_ctx_last_error",
     "vio_ba_solve", "vio_ba_solve_batched", "vio_ba_batch_create", "vio_ba_batch_run",
@@ -37,6 +42,8 @@ EXPORTS = [
     "vio_load_camera_timestamps", "vio_load_imu_csv", "erp_resize_area", "erp_resize_area_device",
     "erp_resize_area_kernel_ms", "erp_tracker_upload_resized",
     "erp_resize_area_any", "erp_resize_area_any_device", "erp_resize_area_tab", "erp_frontend_track_resized",
+    "erp_pixel_bytes", "erp_luma_u8", "erp_ingest", "erp_ingest_device", "erp_ingest_set_route", "erp_ingest_check",
+    "erp_tracker_upload_pixels", "erp_frontend_track_pixels",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -122,6 +129,15 @@ def lib():
     L.erp_resize_area_any_device.argtypes = L.erp_resize_area_device.argtypes
     L.erp_resize_area_tab.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.erp_frontend_track_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.erp_pixel_bytes.argtypes = [C.c_int]
+    L.erp_luma_u8.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp]
+    L.erp_ingest.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+    L.erp_ingest_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                    C.c_int, C.c_int]
+    L.erp_ingest_set_route.argtypes = [vp, C.c_int]
+    L.erp_ingest_check.argtypes = [C.c_int] * 8
+    L.erp_tracker_upload_pixels.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.erp_frontend_track_pixels.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -352,6 +368,46 @@ class Context:
         lib().erp_resize_area_tab(int(ssize), int(dsize), _p(di), _p(si), _p(al), n.value, C.byref(n))
         return di[:n.value], si[:n.value], al[:n.value]
 
+    # ---- colour / packed-YUV frames (VIO_PIX_*, VIO_LUMA_*) ----
+    @staticmethod
+    def pixel_bytes(fmt):
+        """erp_pixel_bytes (host): bytes per pixel of a VIO_PIX_* format."""
+        n = lib().erp_pixel_bytes(int(fmt))
+        if n < 0:
+            raise VioError(f"erp_pixel_bytes({fmt}): unknown pixel format ({n})")
+        return n
+
+    @staticmethod
+    def luma_u8(px, fmt, luma=VIO_LUMA_CVTCOLOR):
+        """erp_luma_u8 (host): the luma of packed pixels, px a (..., bpp) u8 array -> u8 array of shape (...)."""
+        bpp = Context.pixel_bytes(fmt)
+        a = np.ascontiguousarray(px, np.uint8)
+        if bpp > 1 and (a.ndim < 1 or a.shape[-1] != bpp):
+            raise VioError(f"luma_u8: the last axis must hold the {bpp} bytes of a pixel")
+        shape = a.shape[:-1] if bpp > 1 else a.shape
+        out = np.zeros(shape, np.uint8)
+        rc = lib().erp_luma_u8(int(fmt), int(luma), _p(a), out.size, _p(out))
+        if rc:
+            raise VioError(f"erp_luma_u8 failed ({rc})")
+        return out
+
+    def ingest(self, img, fmt, luma, dW, dH):
+        """erp_ingest: luma + cv::resize(..., INTER_AREA) of a packed frame, img an (H, W, bpp) u8 array ((H, W)
+        for GRAY8) whose row stride is honoured, to (dW, dH) no larger than the frame."""
+        a, W, H = _pix_rows(img, self.pixel_bytes(fmt))
+        out = np.zeros((dH, dW), np.uint8)
+        self.check(lib().erp_ingest(self.h, _p(a), int(fmt), int(luma), W, H, a.strides[0], _p(out), dW, dH, dW),
+                   "erp_ingest")
+        return out
+
+    def ingest_device(self, src_ptr, fmt, luma, W, H, stride, n_frames, dst_ptr, dW, dH, dst_stride):
+        self.check(lib().erp_ingest_device(self.h, src_ptr, int(fmt), int(luma), W, H, stride, n_frames, dst_ptr, dW,
+                                           dH, dst_stride), "erp_ingest_device")
+
+    def set_ingest_route(self, route):
+        """erp_ingest_set_route: VIO_INGEST_ROUTE_* of later ingest calls on this context (same bytes)."""
+        self.check(lib().erp_ingest_set_route(self.h, int(route)), "erp_ingest_set_route")
+
     def resize_kernel_ms(self):
         ms = C.c_double()
         self.check(lib().erp_resize_area_kernel_ms(self.h, C.byref(ms)), "erp_resize_area_kernel_ms")
@@ -472,6 +528,21 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _pix_rows(img, bpp):
+    """a packed frame as (u8 array with contiguous rows, W, H); the array's first stride is the row stride"""
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        a = a.astype(np.uint8)
+    if a.ndim == 2 and bpp == 1:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] != bpp:
+        raise VioError(f"a frame of {bpp} bytes per pixel is an (H, W, {bpp}) array, got shape {a.shape}")
+    H, W = a.shape[:2]
+    if a.strides[2] != 1 or a.strides[1] != bpp or a.strides[0] < W * bpp:
+        a = np.ascontiguousarray(a)
+    return a, W, H
+
+
 def ransac_threshold(deg=2.0):
     """threshold_rad = m_ransac_threshold * M_PI / 180.0f (FeatureTracker.cpp:305), as float."""
     return float(np.float32(np.float64(np.float32(deg)) * np.pi / np.float64(np.float32(180.0))))
@@ -562,6 +633,12 @@ class Tracker:
         self.ctx.check(lib().erp_tracker_upload_resized(self.h, slot, _p(img), W, H, img.strides[0]),
                        "erp_tracker_upload_resized")
 
+    def upload_pixels(self, slot, img, fmt, luma=VIO_LUMA_CVTCOLOR):
+        """erp_tracker_upload_pixels: a packed colour / 4:2:2 camera frame, luma + INTER_AREA on the device."""
+        a, W, H = _pix_rows(img, Context.pixel_bytes(fmt))
+        self.ctx.check(lib().erp_tracker_upload_pixels(self.h, slot, _p(a), int(fmt), int(luma), W, H, a.strides[0]),
+                       "erp_tracker_upload_pixels")
+
     def swap(self):
         self.ctx.check(lib().erp_tracker_swap(self.h), "erp_tracker_swap")
 
@@ -641,6 +718,14 @@ class Frontend:
         n = C.c_int()
         self.ctx.check(lib().erp_frontend_track_resized(self.h, _p(img), W, H, img.strides[0], C.byref(n)),
                        "erp_frontend_track_resized")
+        return self._features(n.value)
+
+    def track_pixels(self, img, fmt, luma=VIO_LUMA_CVTCOLOR):
+        """erp_frontend_track_pixels: track on a packed colour / 4:2:2 camera frame."""
+        a, W, H = _pix_rows(img, Context.pixel_bytes(fmt))
+        n = C.c_int()
+        self.ctx.check(lib().erp_frontend_track_pixels(self.h, _p(a), int(fmt), int(luma), W, H, a.strides[0],
+                                                       C.byref(n)), "erp_frontend_track_pixels")
         return self._features(n.value)
 
     def _features(self, count):

@@ -28,6 +28,8 @@ struct vio_ctx {
     // (W, dW, H, dH) of the general INTER_AREA tap tables now in kSlotResizeTabX / kSlotResizeTabY
     int rsz_tab_key[4] = {0, 0, 0, 0};
     int rsz_max_x_taps = 0;  // the largest tap count of a column of those tables
+    // colour ingest execution route (erp_ingest_set_route)
+    int ingest_route = VIO_INGEST_ROUTE_AUTO;
     // monocular initialisation kernels timing (created on first use)
     hipEvent_t init_ev[2] = {nullptr, nullptr};
     // window-BA execution route (vio_ctx_set_ba_route)
@@ -64,6 +66,8 @@ enum { kSlotBaSolve = 19 };
 enum { kSlotGbaSolve = 20 };
 // erp_resize_area_any: the per-output-column / per-output-row tap tables of the general path
 enum { kSlotResizeTabX = 21, kSlotResizeTabY = 22 };
+// erp_ingest_device, two-pass route: the grey camera-resolution plane between the convert and the resize
+enum { kSlotIngestPlane = 23 };
 // pinned host slots: the one-shot solves' input image and every BA download's outputs image
 enum { kHostSlotBaIn = 0, kHostSlotBaOut = 1, kHostSlotGba = 2 };
 

@@ -19,6 +19,11 @@
 // AreaTaps record per output column / row.  tests/resize_general_oracle.py restates this in numpy; the GPU
 // matches it bitwise.
 //
+// erp_ingest[_device] take packed colour (BGR / RGB / BGRA / RGBA) and packed 4:2:2 (YUYV / UYVY) frames: the
+// one-lane-per-pixel kernels are templates on where the u8 value of a source pixel comes from (PixSrc below), and
+// for those formats it is the integer luma of luma_dev.h, computed in registers.  The result is bit for bit
+// erp_resize_area_any of the grey image, which is never stored (tests/ingest_oracle.py).
+//
 // Roofline: HBM-bound streaming, 1 + 1/(fx·fy) bytes per source pixel.  The factor-4 fast path gives
 // each lane 4 output pixels on two output rows: eight 16-byte non-temporal row loads (two 16x4
 // source blocks), no LDS; the grid covers (output row pair, 4-pixel group, frame).
@@ -31,12 +36,76 @@
 #include <vector>
 
 #include "ctx.h"
+#include "luma_dev.h"
 
 namespace vio360 {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
+// Where the one-lane-per-pixel kernels take the u8 value of source pixel x of a row from (erp_ingest*): the grey
+// byte itself, or the luma of a packed pixel, computed in registers.  Everything after that value is the same
+// code, so the fused result equals resize(luma(frame)) bit for bit.
+//   kPixGray    s[x]                                            (the grey kernels: bpp and offsets unused)
+//   kPixByte    s[bpp x + o0]                                   YUYV / UYVY
+//   kPixBytes3  luma(s[bpp x + o0], .. + o1, .. + o2)           BGR / RGB, and BGRA / RGBA at any alignment
+//   kPixDword   one aligned dword at s + 4 x, B G R at bit shifts o0 o1 o2: BGRA / RGBA with src and stride
+//               multiples of 4 (checked on the host)
+//   kPixRun3    BGR / RGB: a lane's run of N consecutive pixels of a row, 3 N bytes, as 3 N / 4 dword loads at
+//               any alignment plus 3 N % 4 byte loads (load_run3); B G R at bit shifts o0 o1 o2 of a pixel's word
+// No variant reads a byte outside [0, W bpp) of a row.
+enum { kPixGray = 0, kPixByte = 1, kPixBytes3 = 2, kPixDword = 3, kPixRun3 = 4 };
+
+struct PixSrc {
+    int bpp, o0, o1, o2;  // o*: byte offsets of B, G, R in a pixel (kPixByte: o0 of the luma byte); kPixDword, kPixRun3: bit shifts
+    int rule;             // VIO_LUMA_*
+};
+
+template <int MODE>
+__device__ __forceinline__ int pix_step(const PixSrc& p) {
+    return MODE == kPixGray ? 1 : (MODE == kPixDword ? 4 : (MODE == kPixRun3 ? 3 : p.bpp));
+}
+
+// the luma of a pixel held in a word, B G R at bit shifts o0 o1 o2
+__device__ __forceinline__ uint8_t word_luma(uint32_t w, const PixSrc& p) {
+    return luma_u8((int)((w >> p.o0) & 0xff), (int)((w >> p.o1) & 0xff), (int)((w >> p.o2) & 0xff), p.rule);
+}
+
+// the 3 N bytes at s (any alignment) into r[0 .. 3 N / 4]: whole dwords first, the last 3 N % 4 bytes one by one,
+// so exactly [s, s + 3 N) is read
+template <int N>
+__device__ __forceinline__ void load_run3(const uint8_t* s, uint32_t (&r)[3 * N / 4 + 1]) {
+    constexpr int kFull = 3 * N / 4;
+#pragma unroll
+    for (int d = 0; d < kFull; ++d) __builtin_memcpy(&r[d], s + 4 * d, 4);
+    r[kFull] = 0;
+#pragma unroll
+    for (int b = 0; b < 3 * N % 4; ++b) r[kFull] |= (uint32_t)s[4 * kFull + b] << (8 * b);
+}
+
+// pixel k of such a run: its three bytes in the low 24 bits
+template <int N>
+__device__ __forceinline__ uint32_t run3_pixel(const uint32_t (&r)[3 * N / 4 + 1], int k) {
+    const int i = 3 * k, d = i >> 2, b = i & 3;  // constants once the caller's loop is unrolled
+    return b <= 1 ? r[d] >> (8 * b) : __builtin_amdgcn_alignbyte(r[d + 1], r[d], b);
+}
+
+// the u8 value of the pixel whose first byte is at s
+template <int MODE>
+__device__ __forceinline__ uint8_t pix_value(const uint8_t* s, const PixSrc& p) {
+    if constexpr (MODE == kPixGray) {
+        return s[0];
+    } else if constexpr (MODE == kPixByte) {
+        return s[p.o0];
+    } else if constexpr (MODE == kPixBytes3) {
+        return luma_u8(s[p.o0], s[p.o1], s[p.o2], p.rule);
+    } else {
+        static_assert(MODE == kPixDword, "kPixRun3 loads runs, not pixels");
+        return word_luma(*reinterpret_cast<const uint32_t*>(s), p);
+    }
+}
+
 struct ResizeArgs {
+    PixSrc px;
     const uint8_t* src;
     int W, H, stride;
     long long frame_bytes_src;
@@ -86,19 +155,51 @@ __global__ __launch_bounds__(256) void resize_area4_kernel(ResizeArgs a) {
     }
 }
 
+// packed -> pitched u8 plane (erp_ingest* with dW == W and dH == H): lane -> 1 pixel
+template <int MODE>
+__global__ __launch_bounds__(256) void ingest_convert_kernel(ResizeArgs a) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    const int f = blockIdx.z;
+    if (x >= a.dW) return;
+    const uint8_t* s = a.src + f * a.frame_bytes_src + (long long)y * a.stride + (long long)x * pix_step<MODE>(a.px);
+    a.dst[f * a.frame_bytes_dst + (long long)y * a.dstride + x] = pix_value<MODE>(s, a.px);
+}
+
 // any integer factors: lane -> 1 output pixel
+template <int MODE>
 __global__ __launch_bounds__(256) void resize_area_kernel(ResizeArgs a) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     const int f = blockIdx.z;
     if (x >= a.dW) return;
-    const uint8_t* s = a.src + f * a.frame_bytes_src + (long long)(a.fy * y) * a.stride + a.fx * x;
+    const int step = pix_step<MODE>(a.px);
+    const uint8_t* s = a.src + f * a.frame_bytes_src + (long long)(a.fy * y) * a.stride + (long long)(a.fx * x) * step;
     int sum = 0;
     for (int k = 0; k < a.fy; ++k)
-        for (int j = 0; j < a.fx; ++j) sum += s[(long long)k * a.stride + j];
+        for (int j = 0; j < a.fx; ++j) sum += pix_value<MODE>(s + (long long)k * a.stride + j * step, a.px);
     // 2x2: ResizeAreaFastVec's (sum + 2) >> 2; every other factor: sum * (1.f / (fx fy)), cvRound
     a.dst[f * a.frame_bytes_dst + (long long)y * a.dstride + x] =
         (a.fx == 2 && a.fy == 2) ? (uint8_t)((sum + 2) >> 2) : area_round(sum, a.scale);
+}
+
+// the same for BGR / RGB with fx = FX: a block row is one run of FX pixels (kPixRun3)
+template <int FX>
+__global__ __launch_bounds__(256) void resize_area_run3_kernel(ResizeArgs a) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    const int f = blockIdx.z;
+    if (x >= a.dW) return;
+    const uint8_t* s = a.src + f * a.frame_bytes_src + (long long)(a.fy * y) * a.stride + (long long)(FX * x) * 3;
+    int sum = 0;
+    for (int k = 0; k < a.fy; ++k) {
+        uint32_t r[3 * FX / 4 + 1];
+        load_run3<FX>(s + (long long)k * a.stride, r);
+#pragma unroll
+        for (int j = 0; j < FX; ++j) sum += word_luma(run3_pixel<FX>(r, j), a.px);
+    }
+    a.dst[f * a.frame_bytes_dst + (long long)y * a.dstride + x] =
+        (FX == 2 && a.fy == 2) ? (uint8_t)((sum + 2) >> 2) : area_round(sum, a.scale);
 }
 
 // the taps of one output column / row of the general path: source indices first .. first + count - 1, weight
@@ -109,8 +210,9 @@ struct AreaTaps {
 };
 
 struct ResizeAnyArgs {
+    PixSrc px;
     const uint8_t* src;
-    int stride;
+    int W, stride;
     long long frame_bytes_src;
     uint8_t* dst;
     int dW, dstride;
@@ -127,8 +229,10 @@ __device__ __forceinline__ float tap_weight(int k, int count, float w_first, flo
 // MAXT > 0 (no column has more than MAXT taps): a row's MAXT byte loads are issued together, a lane with fewer
 // taps repeating its last address, and every lane adds MAXT products with weight 0.f past its last tap
 // (buf + 0.f * v = buf exactly: buf is finite and never -0).  MAXT == 0: any tap count, one load per
-// iteration.
-template <int MAXT>
+// iteration.  kPixRun3 (MAXT > 0, W >= MAXT): every lane loads a run of MAXT pixels, the one that starts at its
+// first tap or, where that would pass the end of the row, the last MAXT pixels of the row; its taps then sit `sh`
+// pixels into the run and the weights before them are 0.f as well (0.f + x = x exactly).
+template <int MAXT, int MODE>
 __global__ __launch_bounds__(256) void resize_area_general_kernel(ResizeAnyArgs a) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
@@ -138,27 +242,43 @@ __global__ __launch_bounds__(256) void resize_area_general_kernel(ResizeAnyArgs 
     const float ax_first = a.tx[x].w_first, ax_mid = a.tx[x].w_mid, ax_last = a.tx[x].w_last;
     const int y0 = a.ty[y].first, ny = a.ty[y].count;
     const float by_first = a.ty[y].w_first, by_mid = a.ty[y].w_mid, by_last = a.ty[y].w_last;
-    const uint8_t* s = a.src + f * a.frame_bytes_src + (long long)y0 * a.stride + x0;
+    const int step = pix_step<MODE>(a.px);
+    const uint8_t* s = a.src + f * a.frame_bytes_src + (long long)y0 * a.stride + (long long)x0 * step;
     float sum = 0.f;
     if constexpr (MAXT > 0) {
         float w[MAXT];
+        if constexpr (MODE == kPixRun3) {
+            const int sh = x0 - min(x0, a.W - MAXT);
+            s -= sh * 3;
 #pragma unroll
-        for (int k = 0; k < MAXT; ++k) w[k] = k < nx ? tap_weight(k, nx, ax_first, ax_mid, ax_last) : 0.f;
+            for (int k = 0; k < MAXT; ++k)
+                w[k] = (k >= sh && k - sh < nx) ? tap_weight(k - sh, nx, ax_first, ax_mid, ax_last) : 0.f;
+        } else {
+#pragma unroll
+            for (int k = 0; k < MAXT; ++k) w[k] = k < nx ? tap_weight(k, nx, ax_first, ax_mid, ax_last) : 0.f;
+        }
         for (int j = 0; j < ny; ++j) {
             uint8_t v[MAXT];
+            if constexpr (MODE == kPixRun3) {
+                uint32_t r[3 * MAXT / 4 + 1];
+                load_run3<MAXT>(s, r);
 #pragma unroll
-            for (int k = 0; k < MAXT; ++k) v[k] = s[min(k, nx - 1)];
+                for (int k = 0; k < MAXT; ++k) v[k] = word_luma(run3_pixel<MAXT>(r, k), a.px);
+            } else {
+#pragma unroll
+                for (int k = 0; k < MAXT; ++k) v[k] = pix_value<MODE>(s + min(k, nx - 1) * step, a.px);
+            }
             float buf = (float)v[0] * w[0];  // = 0.f + it, exactly
 #pragma unroll
             for (int k = 1; k < MAXT; ++k) buf = buf + (float)v[k] * w[k];
             sum = sum + tap_weight(j, ny, by_first, by_mid, by_last) * buf;
             s += a.stride;
         }
-    } else {
+    } else if constexpr (MODE != kPixRun3) {
         for (int j = 0; j < ny; ++j) {
-            float buf = (float)s[0] * ax_first;
-            for (int k = 1; k < nx - 1; ++k) buf = buf + (float)s[k] * ax_mid;
-            if (nx > 1) buf = buf + (float)s[nx - 1] * ax_last;
+            float buf = (float)pix_value<MODE>(s, a.px) * ax_first;
+            for (int k = 1; k < nx - 1; ++k) buf = buf + (float)pix_value<MODE>(s + k * step, a.px) * ax_mid;
+            if (nx > 1) buf = buf + (float)pix_value<MODE>(s + (nx - 1) * step, a.px) * ax_last;
             sum = sum + tap_weight(j, ny, by_first, by_mid, by_last) * buf;
             s += a.stride;
         }
@@ -269,17 +389,18 @@ static int resize_check(int W, int H, int stride, int dW, int dH, int dstride, i
     return VIO_OK;
 }
 
-extern "C" int erp_resize_area_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, int n_frames,
-                                      uint8_t* dst, int dW, int dH, int dst_stride) {
-    if (!ctx || !src || !dst) return VIO_EINVAL;
-    int rc = resize_check(W, H, stride, dW, dH, dst_stride, n_frames);
-    if (rc) {
-        set_error(ctx, rc == VIO_ENOSYS ? "erp_resize_area: only integer downscale factors are supported"
-                                        : "erp_resize_area: bad sizes");
-        return rc;
-    }
-    if (n_frames == 0) return VIO_OK;
+static int resize_events(vio_ctx* ctx) {
+    for (hipEvent_t& ev : ctx->rsz_ev)
+        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
+    return VIO_OK;
+}
+
+static const PixSrc kGrayPix = {1, 0, 0, 0, 0};
+
+static ResizeArgs integer_args(const PixSrc& px, const uint8_t* src, int W, int H, int stride, uint8_t* dst, int dW,
+                               int dH, int dst_stride) {
     ResizeArgs a;
+    a.px = px;
     a.src = src;
     a.W = W;
     a.H = H;
@@ -293,19 +414,49 @@ extern "C" int erp_resize_area_device(vio_ctx* ctx, const uint8_t* src, int W, i
     a.fx = W / dW;
     a.fy = H / dH;
     a.scale = 1.f / (float)(a.fx * a.fy);
-    VIO_DEVICE(ctx);
-    for (hipEvent_t& ev : ctx->rsz_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
-    VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[0], ctx->stream));
-    const bool fast = a.fx == 4 && a.fy == 4 && dW % 4 == 0 && dH % 2 == 0 && stride % 16 == 0 && dst_stride % 4 == 0 &&
-                      (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0;
+    return a;
+}
+
+// the integer-factor kernel of a pixel source on the context stream (grey: the factor-4 kernel where it applies)
+static void launch_integer(vio_ctx* ctx, int mode, const ResizeArgs& a, int n_frames) {
+    const dim3 grid((a.dW + 255) / 256, a.dH, n_frames);
+    const bool fast = mode == kPixGray && a.fx == 4 && a.fy == 4 && a.dW % 4 == 0 && a.dH % 2 == 0 &&
+                      a.stride % 16 == 0 && a.dstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(a.dst) & 3) == 0;
     if (fast) {
-        const int groups = dW / 4;
-        hipLaunchKernelGGL(resize_area4_kernel, dim3((groups + 255) / 256, dH / 2, n_frames), dim3(256), 0, ctx->stream,
+        const int groups = a.dW / 4;
+        hipLaunchKernelGGL(resize_area4_kernel, dim3((groups + 255) / 256, a.dH / 2, n_frames), dim3(256), 0, ctx->stream,
                            a);
-    } else {
-        hipLaunchKernelGGL(resize_area_kernel, dim3((dW + 255) / 256, dH, n_frames), dim3(256), 0, ctx->stream, a);
+    } else if (mode == kPixGray) {
+        hipLaunchKernelGGL(resize_area_kernel<kPixGray>, grid, dim3(256), 0, ctx->stream, a);
+    } else if (mode == kPixByte) {
+        hipLaunchKernelGGL(resize_area_kernel<kPixByte>, grid, dim3(256), 0, ctx->stream, a);
+    } else if (mode == kPixBytes3) {
+        hipLaunchKernelGGL(resize_area_kernel<kPixBytes3>, grid, dim3(256), 0, ctx->stream, a);
+    } else if (mode == kPixDword) {
+        hipLaunchKernelGGL(resize_area_kernel<kPixDword>, grid, dim3(256), 0, ctx->stream, a);
+    } else if (a.fx == 2) {
+        hipLaunchKernelGGL(resize_area_run3_kernel<2>, grid, dim3(256), 0, ctx->stream, a);
+    } else {  // kPixRun3 is chosen for fx 2 and 4 only (ingest_wide_mode)
+        hipLaunchKernelGGL(resize_area_run3_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
     }
+}
+
+extern "C" int erp_resize_area_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, int n_frames,
+                                      uint8_t* dst, int dW, int dH, int dst_stride) {
+    if (!ctx || !src || !dst) return VIO_EINVAL;
+    int rc = resize_check(W, H, stride, dW, dH, dst_stride, n_frames);
+    if (rc) {
+        set_error(ctx, rc == VIO_ENOSYS ? "erp_resize_area: only integer downscale factors are supported"
+                                        : "erp_resize_area: bad sizes");
+        return rc;
+    }
+    if (n_frames == 0) return VIO_OK;
+    const ResizeArgs a = integer_args(kGrayPix, src, W, H, stride, dst, dW, dH, dst_stride);
+    VIO_DEVICE(ctx);
+    if ((rc = resize_events(ctx))) return rc;
+    VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[0], ctx->stream));
+    launch_integer(ctx, kPixGray, a, n_frames);
     VIO_HIP(ctx, hipGetLastError());
     VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[1], ctx->stream));
     return VIO_OK;
@@ -349,6 +500,24 @@ static int resize_any_check(vio_ctx* ctx, int W, int H, int stride, int dW, int 
     return (W % dW || H % dH) ? 1 : 0;
 }
 
+template <int MODE>
+static void launch_general_mode(vio_ctx* ctx, const ResizeAnyArgs& a, const dim3& grid, int max_x_taps) {
+    if (max_x_taps <= 4) hipLaunchKernelGGL((resize_area_general_kernel<4, MODE>), grid, dim3(256), 0, ctx->stream, a);
+    else if (max_x_taps <= 8) hipLaunchKernelGGL((resize_area_general_kernel<8, MODE>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((resize_area_general_kernel<0, MODE>), grid, dim3(256), 0, ctx->stream, a);
+}
+
+// the general kernel of a pixel source on the context stream; a.tx / a.ty / max_x_taps from general_tables
+static void launch_general(vio_ctx* ctx, int mode, const ResizeAnyArgs& a, int dH, int n_frames, int max_x_taps) {
+    const dim3 grid((a.dW + 255) / 256, dH, n_frames);
+    if (mode == kPixGray) launch_general_mode<kPixGray>(ctx, a, grid, max_x_taps);
+    else if (mode == kPixByte) launch_general_mode<kPixByte>(ctx, a, grid, max_x_taps);
+    else if (mode == kPixBytes3) launch_general_mode<kPixBytes3>(ctx, a, grid, max_x_taps);
+    else if (mode == kPixDword) launch_general_mode<kPixDword>(ctx, a, grid, max_x_taps);
+    else if (max_x_taps <= 4) hipLaunchKernelGGL((resize_area_general_kernel<4, kPixRun3>), grid, dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((resize_area_general_kernel<8, kPixRun3>), grid, dim3(256), 0, ctx->stream, a);  // <= 8 (ingest_wide_mode)
+}
+
 extern "C" int erp_resize_area_any_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, int n_frames,
                                           uint8_t* dst, int dW, int dH, int dst_stride) {
     if (!ctx || !src || !dst) return VIO_EINVAL;
@@ -361,20 +530,18 @@ extern "C" int erp_resize_area_any_device(vio_ctx* ctx, const uint8_t* src, int 
     int max_x_taps = 0;
     int rc = general_tables(ctx, W, dW, H, dH, &a.tx, &a.ty, &max_x_taps);
     if (rc) return rc;
+    a.px = kGrayPix;
     a.src = src;
+    a.W = W;
     a.stride = stride;
     a.frame_bytes_src = (long long)stride * H;
     a.dst = dst;
     a.dW = dW;
     a.dstride = dst_stride;
     a.frame_bytes_dst = (long long)dst_stride * dH;
-    for (hipEvent_t& ev : ctx->rsz_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
+    if ((rc = resize_events(ctx))) return rc;
     VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[0], ctx->stream));
-    const dim3 grid((dW + 255) / 256, dH, n_frames);
-    if (max_x_taps <= 4) hipLaunchKernelGGL(resize_area_general_kernel<4>, grid, dim3(256), 0, ctx->stream, a);
-    else if (max_x_taps <= 8) hipLaunchKernelGGL(resize_area_general_kernel<8>, grid, dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(resize_area_general_kernel<0>, grid, dim3(256), 0, ctx->stream, a);
+    launch_general(ctx, kPixGray, a, dH, n_frames, max_x_taps);
     VIO_HIP(ctx, hipGetLastError());
     VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[1], ctx->stream));
     return VIO_OK;
@@ -414,6 +581,223 @@ extern "C" int erp_resize_area_tab(int ssize, int dsize, int32_t* di, int32_t* s
         alpha[i] = tab[i].alpha;
     }
     *n = (int)tab.size();
+    return VIO_OK;
+}
+
+// ---- colour and packed-YUV frames: luma + INTER_AREA (erp_ingest*) ----
+
+extern "C" int erp_pixel_bytes(int format) {
+    switch (format) {
+        case VIO_PIX_GRAY8: return 1;
+        case VIO_PIX_BGR8:
+        case VIO_PIX_RGB8: return 3;
+        case VIO_PIX_BGRA8:
+        case VIO_PIX_RGBA8: return 4;
+        case VIO_PIX_YUYV:
+        case VIO_PIX_UYVY: return 2;
+        default: return VIO_EINVAL;
+    }
+}
+
+static bool pix_is_colour(int format) { return format >= VIO_PIX_BGR8 && format <= VIO_PIX_RGBA8; }
+static bool pix_is_422(int format) { return format == VIO_PIX_YUYV || format == VIO_PIX_UYVY; }
+
+// the byte-variant pixel source of a format (kPixByte / kPixBytes3; GRAY8 is kPixByte at offset 0)
+static PixSrc pix_source(int format, int luma) {
+    PixSrc p = {erp_pixel_bytes(format), 0, 1, 2, luma};
+    if (format == VIO_PIX_RGB8 || format == VIO_PIX_RGBA8) {
+        p.o0 = 2;
+        p.o2 = 0;
+    } else if (format == VIO_PIX_UYVY) {
+        p.o0 = 1;
+    }
+    return p;
+}
+
+static uint8_t pix_value_host(const uint8_t* s, int format, const PixSrc& p) {
+    return pix_is_colour(format) ? luma_u8(s[p.o0], s[p.o1], s[p.o2], p.rule) : s[p.o0];
+}
+
+extern "C" int erp_luma_u8(int format, int luma, const uint8_t* px, int n, uint8_t* out) {
+    if (erp_pixel_bytes(format) < 0 || n < 0 || (n > 0 && (!px || !out))) return VIO_EINVAL;
+    if (pix_is_colour(format) && luma != VIO_LUMA_CVTCOLOR && luma != VIO_LUMA_IMREAD) return VIO_EINVAL;
+    if (pix_is_422(format) && n % 2) return VIO_EINVAL;
+    const PixSrc p = pix_source(format, luma);
+    for (int i = 0; i < n; ++i) out[i] = pix_value_host(px + (size_t)i * p.bpp, format, p);
+    return VIO_OK;
+}
+
+extern "C" int erp_ingest_set_route(vio_ctx* ctx, int route) {
+    if (!ctx || route < VIO_INGEST_ROUTE_AUTO || route > VIO_INGEST_ROUTE_FUSED_BYTES) return VIO_EINVAL;
+    ctx->ingest_route = route;
+    return VIO_OK;
+}
+
+// VIO_INGEST_ROUTE_AUTO: does the one-pass kernel of this pixel source and path (0 integer factors, 1 general)
+// run, or convert + grey resize?  What measured faster (tools/ingest_time.py) at 3840x1920, 4096x2048
+// and 5376x2688 -> 960x480: the one-pass kernel by 2.1x to 4.4x, except for 4-byte pixels that cannot take dword
+// loads (src or stride no multiple of 4), where three byte loads per tap lose to two-pass by 5 % at factor 4 and
+// at 4096 (columns of up to 6 taps in the 8-tap variant) and win by 11 % at 5376 (up to 7 taps).
+static bool ingest_fused_by_default(int mode, int bpp, int path, int max_x_taps) {
+    if (mode == kPixBytes3 && bpp == 4) return path == 1 && max_x_taps > 6;
+    return true;
+}
+
+// The wider-load variant of a byte pixel source, where one applies (else `mode` itself); *px gets its bit shifts.
+// fx: the integer x factor (0: the general path, max_x_taps its widest column; 1: the convert pass).
+//   4-byte pixels: one aligned dword per pixel when src and stride are multiples of 4
+//   3-byte pixels: runs of fx = 2 or 4 pixels, or of the general <4> / <8> kernels' 4 / 8 taps (W no smaller)
+static int ingest_wide_mode(int mode, const uint8_t* src, int stride, int W, int fx, int max_x_taps, PixSrc* px) {
+    if (mode != kPixBytes3) return mode;
+    int wide = mode;
+    if (px->bpp == 4 && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && stride % 4 == 0) wide = kPixDword;
+    if (px->bpp == 3 && (fx == 2 || fx == 4)) wide = kPixRun3;
+    if (px->bpp == 3 && fx == 0 && max_x_taps <= 8 && W >= (max_x_taps <= 4 ? 4 : 8)) wide = kPixRun3;
+    if (wide != mode) {
+        px->o0 *= 8;
+        px->o1 *= 8;
+        px->o2 *= 8;
+    }
+    return wide;
+}
+
+// format, luma rule and sizes of an ingest call: 0 integer factors, 1 the general path, < 0 error (set on ctx)
+static int ingest_check(vio_ctx* ctx, int format, int luma, int W, int H, int stride, int dW, int dH, int dstride,
+                        int n_frames) {
+    const int bpp = erp_pixel_bytes(format);
+    if (bpp < 0) {
+        set_error(ctx, "erp_ingest: unknown pixel format");
+        return VIO_EINVAL;
+    }
+    if (pix_is_colour(format) && luma != VIO_LUMA_CVTCOLOR && luma != VIO_LUMA_IMREAD) {
+        set_error(ctx, "erp_ingest: unknown luma rule");
+        return VIO_EINVAL;
+    }
+    if (W <= 0 || H <= 0 || dW <= 0 || dH <= 0 || (long long)stride < (long long)W * bpp || dstride < dW ||
+        n_frames < 0) {
+        set_error(ctx, "erp_ingest: bad sizes");
+        return VIO_EINVAL;
+    }
+    if (pix_is_422(format) && W % 2) {
+        set_error(ctx, "erp_ingest: a 4:2:2 frame has an even width");
+        return VIO_EINVAL;
+    }
+    if (dW > W || dH > H) {
+        set_error(ctx, "erp_ingest: enlarging is not supported");
+        return VIO_ENOSYS;
+    }
+    if (W % dW || H % dH) return 1;
+    if ((long long)(W / dW) * (H / dH) > (1 << 23)) {  // int block sums
+        set_error(ctx, "erp_ingest: integer factors too large");
+        return VIO_ENOSYS;
+    }
+    return 0;
+}
+
+extern "C" int erp_ingest_check(int format, int luma, int W, int H, int stride, int dW, int dH, int dst_stride) {
+    const int path = ingest_check(nullptr, format, luma, W, H, stride, dW, dH, dst_stride, 1);
+    return path < 0 ? path : VIO_OK;
+}
+
+extern "C" int erp_ingest_device(vio_ctx* ctx, const uint8_t* src, int format, int luma, int W, int H, int stride,
+                                 int n_frames, uint8_t* dst, int dW, int dH, int dst_stride) {
+    if (!ctx || !src || !dst) return VIO_EINVAL;
+    const int path = ingest_check(ctx, format, luma, W, H, stride, dW, dH, dst_stride, n_frames);
+    if (path < 0) return path;
+    if (format == VIO_PIX_GRAY8)
+        return erp_resize_area_any_device(ctx, src, W, H, stride, n_frames, dst, dW, dH, dst_stride);
+    if (n_frames == 0) return VIO_OK;
+    const PixSrc px = pix_source(format, luma);
+    const int mode = pix_is_colour(format) ? kPixBytes3 : kPixByte;
+    const bool convert_only = dW == W && dH == H;
+    const bool bytes_only = ctx->ingest_route == VIO_INGEST_ROUTE_FUSED_BYTES;
+    VIO_DEVICE(ctx);
+    int rc;
+    ResizeAnyArgs g;
+    int max_x_taps = 0;
+    if (path == 1 && (rc = general_tables(ctx, W, dW, H, dH, &g.tx, &g.ty, &max_x_taps))) return rc;
+    // the pixel source of the convert pass (one pixel per lane) and of the fused resize kernel
+    PixSrc cpx = px, fpx = px;
+    const int cmode = bytes_only ? mode : ingest_wide_mode(mode, src, stride, W, 1, 0, &cpx);
+    const int fmode = bytes_only || convert_only ? mode
+                                                 : ingest_wide_mode(mode, src, stride, W, path == 0 ? W / dW : 0,
+                                                                    max_x_taps, &fpx);
+    const bool fused = ctx->ingest_route == VIO_INGEST_ROUTE_AUTO ? ingest_fused_by_default(fmode, px.bpp, path, max_x_taps)
+                                                                  : ctx->ingest_route != VIO_INGEST_ROUTE_TWO_PASS;
+    // two-pass route: the grey plane of every frame, rows padded to 16 bytes (the factor-4 grey kernel's layout)
+    const int pp = (W + 15) & ~15;
+    uint8_t* plane = nullptr;
+    if (!convert_only && !fused) {
+        plane = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotIngestPlane, (size_t)pp * H * n_frames));
+        if (!plane) {
+            set_error(ctx, "erp_ingest: device allocation failed");
+            return VIO_ENOMEM;
+        }
+    }
+    if ((rc = resize_events(ctx))) return rc;
+    VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[0], ctx->stream));
+    const uint8_t* rsrc = src;  // what the resize kernel reads: the packed frames, or the plane
+    int rstride = stride, rmode = fmode;
+    PixSrc rpx = fpx;
+    if (convert_only || !fused) {
+        uint8_t* cdst = convert_only ? dst : plane;
+        const ResizeArgs c = integer_args(cpx, src, W, H, stride, cdst, W, H, convert_only ? dst_stride : pp);
+        const dim3 grid((W + 255) / 256, H, n_frames);
+        if (cmode == kPixByte) hipLaunchKernelGGL(ingest_convert_kernel<kPixByte>, grid, dim3(256), 0, ctx->stream, c);
+        else if (cmode == kPixBytes3) hipLaunchKernelGGL(ingest_convert_kernel<kPixBytes3>, grid, dim3(256), 0, ctx->stream, c);
+        else hipLaunchKernelGGL(ingest_convert_kernel<kPixDword>, grid, dim3(256), 0, ctx->stream, c);
+        VIO_HIP(ctx, hipGetLastError());
+        rsrc = plane;
+        rstride = pp;
+        rmode = kPixGray;
+        rpx = kGrayPix;
+    }
+    if (!convert_only) {
+        if (path == 0) {
+            launch_integer(ctx, rmode, integer_args(rpx, rsrc, W, H, rstride, dst, dW, dH, dst_stride), n_frames);
+        } else {
+            g.px = rpx;
+            g.src = rsrc;
+            g.W = W;
+            g.stride = rstride;
+            g.frame_bytes_src = (long long)rstride * H;
+            g.dst = dst;
+            g.dW = dW;
+            g.dstride = dst_stride;
+            g.frame_bytes_dst = (long long)dst_stride * dH;
+            launch_general(ctx, rmode, g, dH, n_frames, max_x_taps);
+        }
+        VIO_HIP(ctx, hipGetLastError());
+    }
+    VIO_HIP(ctx, hipEventRecord(ctx->rsz_ev[1], ctx->stream));
+    return VIO_OK;
+}
+
+extern "C" int erp_ingest(vio_ctx* ctx, const uint8_t* src, int format, int luma, int W, int H, int stride,
+                          uint8_t* dst, int dW, int dH, int dst_stride) {
+    if (!ctx || !src || !dst) return VIO_EINVAL;
+    const int path = ingest_check(ctx, format, luma, W, H, stride, dW, dH, dst_stride, 1);
+    if (path < 0) return path;
+    if (format == VIO_PIX_GRAY8) return erp_resize_area_any(ctx, src, W, H, stride, dst, dW, dH, dst_stride);
+    const long long row = (long long)W * erp_pixel_bytes(format);
+    const long long sp = (row + 15) & ~15LL;
+    const int dp = (dW + 3) & ~3;
+    if (sp > INT32_MAX) {
+        set_error(ctx, "erp_ingest: bad sizes");
+        return VIO_EINVAL;
+    }
+    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * H));
+    uint8_t* d_dst = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeDst, (size_t)dp * dH));
+    if (!d_src || !d_dst) {
+        set_error(ctx, "erp_ingest: device allocation failed");
+        return VIO_ENOMEM;
+    }
+    VIO_DEVICE(ctx);
+    int rc;
+    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, src, stride, row, H, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = erp_ingest_device(ctx, d_src, format, luma, W, H, (int)sp, 1, d_dst, dW, dH, dp))) return rc;
+    VIO_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, d_dst, dp, dW, dH, hipMemcpyDeviceToHost, ctx->stream));
+    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VIO_OK;
 }
 

@@ -571,6 +571,28 @@ int erp_tracker_upload_resized(erp_tracker* t, int slot, const uint8_t* img, int
     return erp_resize_area_any_device(ctx, d_src, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
 }
 
+int erp_tracker_upload_pixels(erp_tracker* t, int slot, const uint8_t* img, int format, int luma, int W, int H,
+                              int stride) {
+    if (!t || slot < 0 || slot > 1 || !img) return VIO_EINVAL;
+    if (format == VIO_PIX_GRAY8) return erp_tracker_upload_resized(t, slot, img, W, H, stride);
+    vio_ctx* ctx = t->ctx;
+    const int bpp = erp_pixel_bytes(format);
+    if (bpp < 0 || W <= 0 || H <= 0 || (long long)stride < (long long)W * bpp || (long long)W * bpp > (1 << 30)) {
+        set_error(ctx, "erp_tracker_upload_pixels: unknown pixel format or bad sizes");
+        return VIO_EINVAL;
+    }
+    VIO_DEVICE(ctx);
+    const int sp = (W * bpp + 15) & ~15;  // the packed frame, rows padded to 16 bytes (dword loads for 4-byte pixels)
+    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * H));
+    if (!d_src) {
+        set_error(ctx, "erp_tracker_upload_pixels: device allocation failed");
+        return VIO_ENOMEM;
+    }
+    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, (size_t)W * bpp, H, hipMemcpyHostToDevice, ctx->stream));
+    // a frame already at the tracker's size takes the convert-only pass
+    return erp_ingest_device(ctx, d_src, format, luma, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
+}
+
 int erp_tracker_device_frame(erp_tracker* t, int slot, uint8_t** dev_ptr, int* pitch) {
     if (!t || slot < 0 || slot > 1 || !dev_ptr || !pitch) return VIO_EINVAL;
     *dev_ptr = t->lvl[slot][0];
@@ -1149,6 +1171,14 @@ int erp_frontend_track_resized(erp_frontend* f, const uint8_t* img, int W, int H
     if (!f || !img) return VIO_EINVAL;
     int rc;
     if ((rc = erp_tracker_upload_resized(f->t, 1, img, W, H, stride))) return rc;
+    return frontend_track_slot1(f, n_features);
+}
+
+int erp_frontend_track_pixels(erp_frontend* f, const uint8_t* img, int format, int luma, int W, int H, int stride,
+                              int* n_features) {
+    if (!f || !img) return VIO_EINVAL;
+    int rc;
+    if ((rc = erp_tracker_upload_pixels(f->t, 1, img, format, luma, W, H, stride))) return rc;
     return frontend_track_slot1(f, n_features);
 }
 

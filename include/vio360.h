@@ -636,6 +636,51 @@ int erp_resize_area_any_device(vio_ctx* ctx, const uint8_t* src, int W, int H, i
    *n = count (call with cap = 0 to size the buffers). */
 int erp_resize_area_tab(int ssize, int dsize, int32_t* di, int32_t* si, float* alpha, int cap, int* n);
 
+/* Colour and packed-YUV camera frames: luma + INTER_AREA in one pass (csrc/resize.hip).
+   Pixel formats, 1 / 3 / 3 / 4 / 4 / 2 / 2 bytes per pixel; alpha is ignored.  YUYV / UYVY (packed 4:2:2, W
+   even): the luma byte of pixel x is byte 2x / 2x + 1 of the row, taken as is (OpenCV's COLOR_YUV2GRAY_YUY2 /
+   _UYVY); `luma` is ignored, as it is for GRAY8.  NV12 / I420: pass the Y plane as VIO_PIX_GRAY8 with the
+   plane's stride. */
+enum { VIO_PIX_GRAY8 = 0, VIO_PIX_BGR8 = 1, VIO_PIX_RGB8 = 2, VIO_PIX_BGRA8 = 3, VIO_PIX_RGBA8 = 4,
+       VIO_PIX_YUYV = 5, VIO_PIX_UYVY = 6 };
+/* Luma rules of the BGR / RGB formats, integer arithmetic only (restatements: OpenCV is not available to this
+   project, parity with it is unpinned, as for the resize):
+     VIO_LUMA_CVTCOLOR  (3735 B + 19235 G + 9798 R + 16384) >> 15   OpenCV 4.x cvtColor(BGR2GRAY) for u8
+     VIO_LUMA_IMREAD    (1868 B +  9617 G + 4899 R +  8192) >> 14   imread(IMREAD_GRAYSCALE) of a colour PNG,
+                                                                    the reference's own path (app/main.cpp:162,199)
+   Both map (v, v, v) to v; they differ, by 1, on 43 864 of the 2^24 triples. */
+enum { VIO_LUMA_CVTCOLOR = 0, VIO_LUMA_IMREAD = 1 };
+/* host only: bytes per pixel of a format; VIO_EINVAL for an unknown format */
+int erp_pixel_bytes(int format);
+/* host only: the luma of n packed pixels (n even for the 4:2:2 formats) */
+int erp_luma_u8(int format, int luma, const uint8_t* px, int n, uint8_t* out);
+/* erp_resize_area_any of the grey image that the luma rule makes of a packed W x H frame, bit for bit, without
+   that image ever being stored (GRAY8: erp_resize_area_any itself).  stride is in bytes, >= W * bytes per pixel.
+   dW == W and dH == H converts only.  Enlarging on either axis is VIO_ENOSYS; an unknown format or luma rule, an
+   odd W for 4:2:2 and bad sizes are VIO_EINVAL.  Blocking; host buffers. */
+int erp_ingest(vio_ctx* ctx, const uint8_t* src, int format, int luma, int W, int H, int stride, uint8_t* dst,
+               int dW, int dH, int dst_stride);
+/* host only: the argument check of erp_ingest* (one frame) without a context: VIO_OK, or the code they return */
+int erp_ingest_check(int format, int luma, int W, int H, int stride, int dW, int dH, int dst_stride);
+/* the same for n_frames DEVICE frames (frame f at src + f*stride*H, dst + f*dst_stride*dH), async on the context
+   stream; no alignment is required of src or stride.  erp_resize_area_kernel_ms times these launches too. */
+int erp_ingest_device(vio_ctx* ctx, const uint8_t* src, int format, int luma, int W, int H, int stride, int n_frames,
+                      uint8_t* dst, int dW, int dH, int dst_stride);
+/* Execution route of later erp_ingest* calls on this context (diagnostics, tools/ingest_time.py): AUTO picks per
+   format and path what measured faster, FUSED always runs the one-pass kernels, TWO_PASS converts
+   to a grey plane in a context buffer and runs erp_resize_area_any_device on it, FUSED_BYTES runs the one-pass
+   kernels' byte-load variants whatever the format and alignment.  The bytes are the same. */
+enum { VIO_INGEST_ROUTE_AUTO = 0, VIO_INGEST_ROUTE_FUSED = 1, VIO_INGEST_ROUTE_TWO_PASS = 2,
+       VIO_INGEST_ROUTE_FUSED_BYTES = 3 };
+int erp_ingest_set_route(vio_ctx* ctx, int route);
+/* erp_tracker_upload_resized for a packed colour / 4:2:2 frame: upload, then erp_ingest_device into slot's frame
+   (a convert-only pass when the frame is already at the tracker's size) */
+int erp_tracker_upload_pixels(erp_tracker* t, int slot, const uint8_t* img, int format, int luma, int W, int H,
+                              int stride);
+/* erp_frontend_track_resized for a packed colour / 4:2:2 frame */
+int erp_frontend_track_pixels(erp_frontend* f, const uint8_t* img, int format, int luma, int W, int H, int stride,
+                              int* n_features);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

@@ -23,6 +23,10 @@ _lib = None
 VIO_PIX_GRAY8, VIO_PIX_BGR8, VIO_PIX_RGB8, VIO_PIX_BGRA8, VIO_PIX_RGBA8, VIO_PIX_YUYV, VIO_PIX_UYVY = range(7)
 VIO_LUMA_CVTCOLOR, VIO_LUMA_IMREAD = 0, 1
 VIO_INGEST_ROUTE_AUTO, VIO_INGEST_ROUTE_FUSED, VIO_INGEST_ROUTE_TWO_PASS, VIO_INGEST_ROUTE_FUSED_BYTES = range(4)
+# border modes of the lens-to-ERP warp, per axis
+VIO_WARP_X_CONSTANT, VIO_WARP_X_WRAP = 0, 1
+VIO_WARP_Y_CONSTANT, VIO_WARP_Y_REPLICATE = 0, 2
+VIO_WARP_ROUTE_AUTO, VIO_WARP_ROUTE_SINGLE = 0, 1
 
 EXPORTS = [
     "vio_abi_version", "vio_ctx_create", "vio_ctx_destroy", "vio_ctx_last_error",
@@ -44,6 +48,9 @@ EXPORTS = [
     "erp_resize_area_any", "erp_resize_area_any_device", "erp_resize_area_tab", "erp_frontend_track_resized",
     "erp_pixel_bytes", "erp_luma_u8", "erp_ingest", "erp_ingest_device", "erp_ingest_set_route", "erp_ingest_check",
     "erp_tracker_upload_pixels", "erp_frontend_track_pixels",
+    "erp_warp_create", "erp_warp_destroy", "erp_warp_quantize", "erp_warp_check", "erp_warp_apply",
+    "erp_warp_apply_device", "erp_warp_kernel_ms", "erp_warp_set_route", "erp_warp_map_erp",
+    "erp_warp_map_fisheye", "erp_warp_map_cubemap", "erp_tracker_upload_warped", "erp_frontend_track_warped",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -138,6 +145,22 @@ def lib():
     L.erp_ingest_check.argtypes = [C.c_int] * 8
     L.erp_tracker_upload_pixels.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.erp_frontend_track_pixels.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.erp_warp_create.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(C.c_void_p)]
+    L.erp_warp_destroy.argtypes = [vp]
+    L.erp_warp_destroy.restype = None
+    L.erp_warp_quantize.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.erp_warp_check.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.erp_warp_apply.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    L.erp_warp_apply_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    L.erp_warp_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.erp_warp_set_route.argtypes = [vp, C.c_int]
+    L.erp_warp_map_erp.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    L.erp_warp_map_fisheye.argtypes = [C.POINTER(abi.ErpFisheyeLens), C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    L.erp_warp_map_cubemap.argtypes = [C.POINTER(abi.ErpCubeFace), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                       C.c_int, vp, vp]
+    L.erp_tracker_upload_warped.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]
+    L.erp_frontend_track_warped.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -408,6 +431,13 @@ class Context:
         """erp_ingest_set_route: VIO_INGEST_ROUTE_* of later ingest calls on this context (same bytes)."""
         self.check(lib().erp_ingest_set_route(self.h, int(route)), "erp_ingest_set_route")
 
+    # ---- lens-to-ERP warp ----
+    def warp_create(self, map_x, map_y, sW, sH, border_x=VIO_WARP_X_CONSTANT, border_y=VIO_WARP_Y_CONSTANT,
+                    border_value=0):
+        """erp_warp_create: a Warp from float32 (dH, dW) source-coordinate maps (cv::remap's map1 / map2) into an
+        sW x sH source frame; the maps' common row stride is honoured."""
+        return Warp(self, map_x, map_y, sW, sH, border_x, border_y, border_value)
+
     def resize_kernel_ms(self):
         ms = C.c_double()
         self.check(lib().erp_resize_area_kernel_ms(self.h, C.byref(ms)), "erp_resize_area_kernel_ms")
@@ -543,6 +573,65 @@ def _pix_rows(img, bpp):
     return a, W, H
 
 
+def warp_quantize(s, S, border_mode):
+    """erp_warp_quantize (host): float32 coordinates of an axis of size S -> (q int32, valid u8)."""
+    a = np.ascontiguousarray(s, np.float32).reshape(-1)
+    q, valid = np.zeros(a.size, np.int32), np.zeros(a.size, np.uint8)
+    rc = lib().erp_warp_quantize(_p(a), a.size, int(S), int(border_mode), _p(q), _p(valid))
+    if rc:
+        raise VioError(f"erp_warp_quantize failed ({rc})")
+    return q, valid
+
+
+def _rot9(R):
+    if R is None:
+        return None, None
+    a = np.ascontiguousarray(R, np.float64).reshape(-1)
+    if a.size != 9:
+        raise VioError("a rotation is 9 doubles, row-major")
+    return a, _p(a)
+
+
+def warp_map_erp(sW, sH, dW, dH, R_dst=None):
+    """erp_warp_map_erp (host): (map_x, map_y), float32 (dH, dW), of a rotated / resampled sW x sH ERP source."""
+    mx, my = np.zeros((dH, dW), np.float32), np.zeros((dH, dW), np.float32)
+    keep, r = _rot9(R_dst)
+    rc = lib().erp_warp_map_erp(int(sW), int(sH), r, int(dW), int(dH), _p(mx), _p(my))
+    if rc:
+        raise VioError(f"erp_warp_map_erp failed ({rc})")
+    return mx, my
+
+
+def warp_map_fisheye(lenses, dW, dH, R_dst=None):
+    """erp_warp_map_fisheye (host): lenses a list of dicts {R (3x3, rig -> lens), cx, cy, f, theta_max}."""
+    arr = (abi.ErpFisheyeLens * max(len(lenses), 1))()
+    for k, l in enumerate(lenses):
+        arr[k].R[:] = [float(v) for v in np.asarray(l["R"], np.float64).reshape(9)]
+        arr[k].cx, arr[k].cy, arr[k].f, arr[k].theta_max = (float(l[n]) for n in ("cx", "cy", "f", "theta_max"))
+    mx, my = np.zeros((dH, dW), np.float32), np.zeros((dH, dW), np.float32)
+    keep, r = _rot9(R_dst)
+    rc = lib().erp_warp_map_fisheye(arr, len(lenses), r, int(dW), int(dH), _p(mx), _p(my))
+    if rc:
+        raise VioError(f"erp_warp_map_fisheye failed ({rc})")
+    return mx, my
+
+
+def warp_map_cubemap(faces, eac, sW, sH, dW, dH, R_dst=None):
+    """erp_warp_map_cubemap (host): faces a list of dicts {R (3x3, rig -> face), x0, y0, w, h} in an sW x sH source;
+    eac: equi-angular cubemap."""
+    arr = (abi.ErpCubeFace * max(len(faces), 1))()
+    for k, f in enumerate(faces):
+        arr[k].R[:] = [float(v) for v in np.asarray(f["R"], np.float64).reshape(9)]
+        arr[k].x0, arr[k].y0, arr[k].w, arr[k].h = (int(f[n]) for n in ("x0", "y0", "w", "h"))
+    mx, my = np.zeros((dH, dW), np.float32), np.zeros((dH, dW), np.float32)
+    keep, r = _rot9(R_dst)
+    rc = lib().erp_warp_map_cubemap(arr, len(faces), 1 if eac else 0, int(sW), int(sH), r, int(dW), int(dH), _p(mx),
+                                    _p(my))
+    if rc:
+        raise VioError(f"erp_warp_map_cubemap failed ({rc})")
+    return mx, my
+
+
 def ransac_threshold(deg=2.0):
     """threshold_rad = m_ransac_threshold * M_PI / 180.0f (FeatureTracker.cpp:305), as float."""
     return float(np.float32(np.float64(np.float32(deg)) * np.pi / np.float64(np.float32(180.0))))
@@ -610,6 +699,66 @@ def ransac_samples(seed, n, iters=1000):
     return out
 
 
+class Warp:
+    """erp_warp_*: a device-resident quantised map (cv::remap INTER_LINEAR in integer arithmetic, fused luma)."""
+
+    def __init__(self, ctx, map_x, map_y, sW, sH, border_x, border_y, border_value=0):
+        mx, my = np.asarray(map_x, np.float32), np.asarray(map_y, np.float32)
+        if mx.ndim != 2 or mx.shape != my.shape:
+            raise VioError(f"map_x and map_y are (dH, dW) arrays of one shape, got {mx.shape} and {my.shape}")
+        if mx.strides != my.strides or mx.strides[1] != 4 or mx.strides[0] % 4 or mx.strides[0] < 4 * mx.shape[1]:
+            mx, my = np.ascontiguousarray(mx), np.ascontiguousarray(my)
+        self.ctx, self.sW, self.sH = ctx, int(sW), int(sH)
+        self.dH, self.dW = mx.shape
+        h = C.c_void_p()
+        ctx.check(lib().erp_warp_create(ctx.h, _p(mx), _p(my), self.dW, self.dH, mx.strides[0] // 4, self.sW, self.sH,
+                                        int(border_x), int(border_y), int(border_value), C.byref(h)), "erp_warp_create")
+        self.h = h
+        ctx._children.add(self)
+
+    def _frame(self, img, fmt):
+        a, W, H = _pix_rows(img, Context.pixel_bytes(fmt))
+        if (W, H) != (self.sW, self.sH):
+            raise VioError(f"the warp's source is {self.sW} x {self.sH}, got a {W} x {H} frame")
+        return a
+
+    def apply(self, img, fmt=VIO_PIX_GRAY8, luma=VIO_LUMA_CVTCOLOR):
+        """erp_warp_apply: img an (sH, sW, bpp) u8 frame ((sH, sW) for GRAY8), row stride honoured -> (dH, dW) u8."""
+        a = self._frame(img, fmt)
+        out = np.zeros((self.dH, self.dW), np.uint8)
+        self.ctx.check(lib().erp_warp_apply(self.h, _p(a), int(fmt), int(luma), a.strides[0], _p(out), self.dW),
+                       "erp_warp_apply")
+        return out
+
+    def apply_device(self, src_ptr, fmt, luma, stride, n_frames, dst_ptr, dst_stride):
+        self.ctx.check(lib().erp_warp_apply_device(self.h, src_ptr, int(fmt), int(luma), stride, n_frames, dst_ptr,
+                                                   dst_stride), "erp_warp_apply_device")
+
+    def check(self, fmt, luma, stride, dst_stride):
+        """erp_warp_check (host): the code erp_warp_apply* would return for these arguments."""
+        return lib().erp_warp_check(self.h, int(fmt), int(luma), int(stride), int(dst_stride))
+
+    def set_route(self, route):
+        """erp_warp_set_route: VIO_WARP_ROUTE_* of later applies of this warp (same bytes)."""
+        self.ctx.check(lib().erp_warp_set_route(self.h, int(route)), "erp_warp_set_route")
+
+    def kernel_ms(self):
+        ms = C.c_double()
+        self.ctx.check(lib().erp_warp_kernel_ms(self.h, C.byref(ms)), "erp_warp_kernel_ms")
+        return ms.value
+
+    def close(self):
+        if self.h:
+            lib().erp_warp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Tracker:
     """Device-resident frame pipeline (erp_tracker_*): pyramids + LK + RANSAC + GFTT re-detection."""
 
@@ -638,6 +787,13 @@ class Tracker:
         a, W, H = _pix_rows(img, Context.pixel_bytes(fmt))
         self.ctx.check(lib().erp_tracker_upload_pixels(self.h, slot, _p(a), int(fmt), int(luma), W, H, a.strides[0]),
                        "erp_tracker_upload_pixels")
+
+    def upload_warped(self, slot, warp, img, fmt=VIO_PIX_GRAY8, luma=VIO_LUMA_CVTCOLOR):
+        """erp_tracker_upload_warped: a camera frame that `warp` takes to ERP on the device (and INTER_AREA to the
+        tracker's size when the warp's destination is larger)."""
+        a = warp._frame(img, fmt)
+        self.ctx.check(lib().erp_tracker_upload_warped(self.h, slot, warp.h, _p(a), int(fmt), int(luma), a.strides[0]),
+                       "erp_tracker_upload_warped")
 
     def swap(self):
         self.ctx.check(lib().erp_tracker_swap(self.h), "erp_tracker_swap")
@@ -726,6 +882,14 @@ class Frontend:
         n = C.c_int()
         self.ctx.check(lib().erp_frontend_track_pixels(self.h, _p(a), int(fmt), int(luma), W, H, a.strides[0],
                                                        C.byref(n)), "erp_frontend_track_pixels")
+        return self._features(n.value)
+
+    def track_warped(self, warp, img, fmt=VIO_PIX_GRAY8, luma=VIO_LUMA_CVTCOLOR):
+        """erp_frontend_track_warped: track on a camera frame that `warp` takes to ERP on the device."""
+        a = warp._frame(img, fmt)
+        n = C.c_int()
+        self.ctx.check(lib().erp_frontend_track_warped(self.h, warp.h, _p(a), int(fmt), int(luma), a.strides[0],
+                                                       C.byref(n)), "erp_frontend_track_warped")
         return self._features(n.value)
 
     def _features(self, count):

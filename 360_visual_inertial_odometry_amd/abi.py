@@ -600,3 +600,13 @@ class VioWindowKfStats(C.Structure):
 class VioWindowMappointInfo(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("bad", C.c_int32), ("marginalized", C.c_int32), ("triangulated", C.c_int32),
                 ("reference_frame", C.c_int32), ("num_observations", C.c_int32)]
+
+
+# ---- lens-to-ERP warp: the generators' lens / face tables (include/vio360.h) ----
+class ErpFisheyeLens(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("cx", C.c_double), ("cy", C.c_double), ("f", C.c_double),
+                ("theta_max", C.c_double)]
+
+
+class ErpCubeFace(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]

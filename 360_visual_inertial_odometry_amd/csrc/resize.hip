@@ -20,7 +20,7 @@
 // matches it bitwise.
 //
 // erp_ingest[_device] take packed colour (BGR / RGB / BGRA / RGBA) and packed 4:2:2 (YUYV / UYVY) frames: the
-// one-lane-per-pixel kernels are templates on where the u8 value of a source pixel comes from (PixSrc below), and
+// one-lane-per-pixel kernels are templates on where the u8 value of a source pixel comes from (PixSrc, pix_dev.h), and
 // for those formats it is the integer luma of luma_dev.h, computed in registers.  The result is bit for bit
 // erp_resize_area_any of the grey image, which is never stored (tests/ingest_oracle.py).
 //
@@ -37,38 +37,13 @@
 
 #include "ctx.h"
 #include "luma_dev.h"
+#include "pix_dev.h"
 
 namespace vio360 {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// Where the one-lane-per-pixel kernels take the u8 value of source pixel x of a row from (erp_ingest*): the grey
-// byte itself, or the luma of a packed pixel, computed in registers.  Everything after that value is the same
-// code, so the fused result equals resize(luma(frame)) bit for bit.
-//   kPixGray    s[x]                                            (the grey kernels: bpp and offsets unused)
-//   kPixByte    s[bpp x + o0]                                   YUYV / UYVY
-//   kPixBytes3  luma(s[bpp x + o0], .. + o1, .. + o2)           BGR / RGB, and BGRA / RGBA at any alignment
-//   kPixDword   one aligned dword at s + 4 x, B G R at bit shifts o0 o1 o2: BGRA / RGBA with src and stride
-//               multiples of 4 (checked on the host)
-//   kPixRun3    BGR / RGB: a lane's run of N consecutive pixels of a row, 3 N bytes, as 3 N / 4 dword loads at
-//               any alignment plus 3 N % 4 byte loads (load_run3); B G R at bit shifts o0 o1 o2 of a pixel's word
-// No variant reads a byte outside [0, W bpp) of a row.
-enum { kPixGray = 0, kPixByte = 1, kPixBytes3 = 2, kPixDword = 3, kPixRun3 = 4 };
-
-struct PixSrc {
-    int bpp, o0, o1, o2;  // o*: byte offsets of B, G, R in a pixel (kPixByte: o0 of the luma byte); kPixDword, kPixRun3: bit shifts
-    int rule;             // VIO_LUMA_*
-};
-
-template <int MODE>
-__device__ __forceinline__ int pix_step(const PixSrc& p) {
-    return MODE == kPixGray ? 1 : (MODE == kPixDword ? 4 : (MODE == kPixRun3 ? 3 : p.bpp));
-}
-
-// the luma of a pixel held in a word, B G R at bit shifts o0 o1 o2
-__device__ __forceinline__ uint8_t word_luma(uint32_t w, const PixSrc& p) {
-    return luma_u8((int)((w >> p.o0) & 0xff), (int)((w >> p.o1) & 0xff), (int)((w >> p.o2) & 0xff), p.rule);
-}
+// Where the one-lane-per-pixel kernels take the u8 value of a source pixel from: PixSrc / pix_value of pix_dev.h.
 
 // the 3 N bytes at s (any alignment) into r[0 .. 3 N / 4]: whole dwords first, the last 3 N % 4 bytes one by one,
 // so exactly [s, s + 3 N) is read
@@ -87,21 +62,6 @@ template <int N>
 __device__ __forceinline__ uint32_t run3_pixel(const uint32_t (&r)[3 * N / 4 + 1], int k) {
     const int i = 3 * k, d = i >> 2, b = i & 3;  // constants once the caller's loop is unrolled
     return b <= 1 ? r[d] >> (8 * b) : __builtin_amdgcn_alignbyte(r[d + 1], r[d], b);
-}
-
-// the u8 value of the pixel whose first byte is at s
-template <int MODE>
-__device__ __forceinline__ uint8_t pix_value(const uint8_t* s, const PixSrc& p) {
-    if constexpr (MODE == kPixGray) {
-        return s[0];
-    } else if constexpr (MODE == kPixByte) {
-        return s[p.o0];
-    } else if constexpr (MODE == kPixBytes3) {
-        return luma_u8(s[p.o0], s[p.o1], s[p.o2], p.rule);
-    } else {
-        static_assert(MODE == kPixDword, "kPixRun3 loads runs, not pixels");
-        return word_luma(*reinterpret_cast<const uint32_t*>(s), p);
-    }
 }
 
 struct ResizeArgs {
@@ -597,21 +557,6 @@ extern "C" int erp_pixel_bytes(int format) {
         case VIO_PIX_UYVY: return 2;
         default: return VIO_EINVAL;
     }
-}
-
-static bool pix_is_colour(int format) { return format >= VIO_PIX_BGR8 && format <= VIO_PIX_RGBA8; }
-static bool pix_is_422(int format) { return format == VIO_PIX_YUYV || format == VIO_PIX_UYVY; }
-
-// the byte-variant pixel source of a format (kPixByte / kPixBytes3; GRAY8 is kPixByte at offset 0)
-static PixSrc pix_source(int format, int luma) {
-    PixSrc p = {erp_pixel_bytes(format), 0, 1, 2, luma};
-    if (format == VIO_PIX_RGB8 || format == VIO_PIX_RGBA8) {
-        p.o0 = 2;
-        p.o2 = 0;
-    } else if (format == VIO_PIX_UYVY) {
-        p.o0 = 1;
-    }
-    return p;
 }
 
 static uint8_t pix_value_host(const uint8_t* s, int format, const PixSrc& p) {

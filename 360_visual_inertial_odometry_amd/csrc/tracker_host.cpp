@@ -18,6 +18,7 @@
 
 #include "ctx.h"
 #include "tracker_types.h"
+#include "warp.h"
 
 using namespace vio360;
 
@@ -591,6 +592,42 @@ int erp_tracker_upload_pixels(erp_tracker* t, int slot, const uint8_t* img, int 
     VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, (size_t)W * bpp, H, hipMemcpyHostToDevice, ctx->stream));
     // a frame already at the tracker's size takes the convert-only pass
     return erp_ingest_device(ctx, d_src, format, luma, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
+}
+
+int erp_tracker_upload_warped(erp_tracker* t, int slot, erp_warp* w, const uint8_t* img, int format, int luma,
+                              int stride) {
+    if (!t || slot < 0 || slot > 1 || !w || !img) return VIO_EINVAL;
+    vio_ctx* ctx = t->ctx;
+    if (w->ctx != ctx) {
+        set_error(ctx, "erp_tracker_upload_warped: the warp belongs to another context");
+        return VIO_EINVAL;
+    }
+    int rc;
+    if ((rc = erp_warp_check(w, format, luma, stride, w->dW))) return rc;
+    if (w->dW < t->W || w->dH < t->H) {
+        set_error(ctx, "erp_tracker_upload_warped: the warp's destination is smaller than the tracker's frame");
+        return VIO_ENOSYS;
+    }
+    const long long row = (long long)w->sW * erp_pixel_bytes(format);
+    if (row > (1 << 30)) {
+        set_error(ctx, "erp_tracker_upload_warped: bad sizes");
+        return VIO_EINVAL;
+    }
+    VIO_DEVICE(ctx);
+    const int sp = (int)((row + 15) & ~15LL);  // the packed frame, rows padded to 16 bytes (dword loads for 4-byte pixels)
+    const bool direct = w->dW == t->W && w->dH == t->H;
+    const int wp = (w->dW + 15) & ~15;  // supersampled route: 16-byte rows, the resize fast path
+    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * w->sH));
+    uint8_t* d_warp = direct ? nullptr : static_cast<uint8_t*>(ctx_buffer(ctx, kSlotWarpDst, (size_t)wp * w->dH));
+    if (!d_src || (!direct && !d_warp)) {
+        set_error(ctx, "erp_tracker_upload_warped: device allocation failed");
+        return VIO_ENOMEM;
+    }
+    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, (size_t)row, w->sH, hipMemcpyHostToDevice, ctx->stream));
+    if (direct) return erp_warp_apply_device(w, d_src, format, luma, sp, 1, t->lvl[slot][0], t->lp[0]);
+    // remap at the warp's size, then cv::resize(..., INTER_AREA) into the slot
+    if ((rc = erp_warp_apply_device(w, d_src, format, luma, sp, 1, d_warp, wp))) return rc;
+    return erp_resize_area_any_device(ctx, d_warp, w->dW, w->dH, wp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
 }
 
 int erp_tracker_device_frame(erp_tracker* t, int slot, uint8_t** dev_ptr, int* pitch) {
@@ -1179,6 +1216,14 @@ int erp_frontend_track_pixels(erp_frontend* f, const uint8_t* img, int format, i
     if (!f || !img) return VIO_EINVAL;
     int rc;
     if ((rc = erp_tracker_upload_pixels(f->t, 1, img, format, luma, W, H, stride))) return rc;
+    return frontend_track_slot1(f, n_features);
+}
+
+int erp_frontend_track_warped(erp_frontend* f, erp_warp* w, const uint8_t* img, int format, int luma, int stride,
+                              int* n_features) {
+    if (!f || !w || !img) return VIO_EINVAL;
+    int rc;
+    if ((rc = erp_tracker_upload_warped(f->t, 1, w, img, format, luma, stride))) return rc;
     return frontend_track_slot1(f, n_features);
 }
 

@@ -681,6 +681,99 @@ int erp_tracker_upload_pixels(erp_tracker* t, int slot, const uint8_t* img, int 
 int erp_frontend_track_pixels(erp_frontend* f, const uint8_t* img, int format, int luma, int W, int H, int stride,
                               int* n_features);
 
+/* Lens-to-ERP warp: cv::remap(src, dst, map_x, map_y, INTER_LINEAR) restated in exact integer arithmetic and
+   fused with the luma rules above (csrc/warp.hip).  The map gives destination pixel (x, y) of a
+   dW x dH u8 frame the source coordinate (map_x, map_y)[y * map_stride + x] as float32.  OpenCV is not available
+   to this project: parity with it is unpinned, as for the resize and the luma rules; the contract is this text
+   and tests/warp_oracle.py, which the GPU matches bitwise.
+     quantisation (host, once per map)   q = lrint((double)s * 32.0), round half to even; i = q >> 5 (floor),
+                                         a = q & 31; a non-finite map_x or map_y makes the pixel invalid
+     borders, per axis                   X_WRAP: tap columns modulo sW (a full ERP source), q reduced to
+                                         [0, 32 sW); Y_REPLICATE: tap rows clamped to [0, sH); CONSTANT: a tap
+                                         outside the source reads border_value (q clamped to [-32, 32 S], which
+                                         changes no result); an invalid pixel is border_value whatever the modes
+     taps                                p00 = (ix, iy), p01 = (ix + 1, iy), p10 = (ix, iy + 1), p11 = (ix + 1,
+                                         iy + 1), each the luma (erp_luma_u8) of that source pixel; a, b the
+                                         fractional bits of x and y
+     pixel                               ((32-a)(32-b) p00 + a(32-b) p01 + (32-a)b p10 + ab p11 + 512) >> 10
+   (OpenCV's INTER_BITS = 5 fixed-point bilinear weights with the common factor 32 divided out: the four weights
+   are exact integers that sum to 1024.)  So warp(frame) == warp(grey(frame)) bit for bit, and the grey image is
+   never stored. */
+enum { VIO_WARP_X_CONSTANT = 0, VIO_WARP_X_WRAP = 1 };
+enum { VIO_WARP_Y_CONSTANT = 0, VIO_WARP_Y_REPLICATE = 2 };
+/* device-resident quantised map, bound to a context; destroy it before the context */
+typedef struct erp_warp erp_warp;
+/* map_stride in floats, >= dW; dH at most 65535; sW x sH the source frame in pixels (each at most 2^25); border_x a VIO_WARP_X_*,
+   border_y a VIO_WARP_Y_*, border_value in [0, 255].  Blocking (quantises on the host, uploads the map).  ctx ==
+   NULL gives a host-only object (no map is kept) that erp_warp_check and erp_warp_destroy accept and every other
+   call refuses with VIO_EINVAL: the argument checks then need no device. */
+int erp_warp_create(vio_ctx* ctx, const float* map_x, const float* map_y, int dW, int dH, int map_stride, int sW,
+                    int sH, int border_x, int border_y, int border_value, erp_warp** out);
+void erp_warp_destroy(erp_warp* w);
+/* host only: the quantisation of n coordinates of one axis of size S under border_mode (a VIO_WARP_X_* or
+   VIO_WARP_Y_*): q[i], and valid[i] = 0 (with q[i] = 0) for a non-finite coordinate */
+int erp_warp_quantize(const float* s, int n, int S, int border_mode, int32_t* q, uint8_t* valid);
+/* host only: the argument check of erp_warp_apply* (format, luma, stride in bytes, dst_stride): VIO_OK, or the
+   code they return (unknown format or luma rule, odd sW for 4:2:2, stride < sW * bytes per pixel, dst_stride < dW) */
+int erp_warp_check(const erp_warp* w, int format, int luma, int stride, int dst_stride);
+/* one sW x sH frame of `format` -> dst (dW x dH u8).  Blocking; host buffers. */
+int erp_warp_apply(erp_warp* w, const uint8_t* src, int format, int luma, int stride, uint8_t* dst, int dst_stride);
+/* the same for n_frames DEVICE frames (frame f at src + f*stride*sH, dst + f*dst_stride*dH) in one launch that
+   reads the map once, async on the context stream; no alignment is required of src, stride or dst, and the
+   padding of the destination rows is not written */
+int erp_warp_apply_device(erp_warp* w, const uint8_t* src, int format, int luma, int stride, int n_frames,
+                          uint8_t* dst, int dst_stride);
+/* device time (ms) of the last warp launch of this object (waits for it) */
+int erp_warp_kernel_ms(erp_warp* w, double* ms);
+/* Execution route of later applies of this object (diagnostics, tools/warp_time.py): AUTO loads the two taps of a
+   source row as one pair of neighbouring pixels (every format, any alignment; sources one pixel wide run SINGLE),
+   SINGLE loads every tap on its own (4-byte pixels: one aligned dword when src and stride are multiples of 4, else
+   byte loads).  The bytes are the same. */
+enum { VIO_WARP_ROUTE_AUTO = 0, VIO_WARP_ROUTE_SINGLE = 1 };
+int erp_warp_set_route(erp_warp* w, int route);
+
+/* Map generators: host only, computed in double, written as float32 map_x / map_y of dW * dH entries (row-major,
+   stride dW).  Destination pixel (x, y) has the bearing of Camera::PixelToBearing (src/database/Camera.cpp:22-47)
+   at u = x, v = y, no half-pixel offset (as the tracker reads coordinates); R_dst (9 doubles, row-major, NULL =
+   identity) rotates it into the source rig frame: b = R_dst * bearing.  Bad sizes or tables are VIO_EINVAL. */
+/* a rotated / resampled ERP source: Camera::BearingToPixel (Camera.cpp:49-67) into sW x sH; use with X_WRAP +
+   Y_REPLICATE (e.g. R_dst = Rwg of vio_imu_init_solve: a gravity-aligned frame) */
+int erp_warp_map_erp(int sW, int sH, const double* R_dst, int dW, int dH, float* map_x, float* map_y);
+/* equidistant fisheye lenses (dual-fisheye 360 cameras: two lenses, side by side in one image or one table per
+   image).  R is rig -> lens, the lens looks along +Z, X right, Y down: bl = R b, h = hypot(bl.x, bl.y), theta =
+   atan2(h, bl.z); the pixel takes the lens of smallest theta among those with theta <= theta_max (ties: lowest
+   index): sx = cx + f theta bl.x / h, sy = cy + f theta bl.y / h ((cx, cy) at h = 0); no lens: NaN (invalid).  The
+   seam between lenses is hard (no blending). */
+typedef struct {
+    double R[9];
+    double cx, cy, f, theta_max; /* centre (px), focal length (px / rad), half field of view (rad) */
+} erp_fisheye_lens;
+int erp_warp_map_fisheye(const erp_fisheye_lens* lenses, int n, const double* R_dst, int dW, int dH, float* map_x,
+                         float* map_y);
+/* cubemap faces, any layout (3x2, 6x1, cross) as a face table: R is rig -> face, the face looks along +Z and
+   fills the w x h rectangle at (x0, y0) of the sW x sH source.  The pixel takes the face of largest (R b).z (ties:
+   lowest index; NaN if none is positive): u = bx / bz, v = by / bz, with eac != 0 each becomes (4/pi) atan(.)
+   (equi-angular cubemap); sx = x0 + (u + 1) w / 2 - 0.5 clamped to [x0, x0 + w - 1], sy likewise: every tap stays
+   inside the face.  A face outside the source is VIO_EINVAL. */
+typedef struct {
+    double R[9];
+    int32_t x0, y0, w, h;
+} erp_cube_face;
+int erp_warp_map_cubemap(const erp_cube_face* faces, int n, int eac, int sW, int sH, const double* R_dst, int dW,
+                         int dH, float* map_x, float* map_y);
+
+/* erp_tracker_upload for a frame that needs a warp first: img is the warp's sW x sH source frame (host), and the
+   warped frame lands in slot's frame without a host round trip.  A warp of the tracker's size writes the slot
+   directly; a larger one (supersampling: a 5.7K fisheye pair taken to 960x480 with bilinear taps alone would
+   alias) is warped into a context buffer and erp_resize_area_any_device takes it into the slot, i.e. remap then
+   resize(INTER_AREA); a warp smaller than the tracker on either axis is VIO_ENOSYS; a warp of another context is
+   VIO_EINVAL. */
+int erp_tracker_upload_warped(erp_tracker* t, int slot, erp_warp* w, const uint8_t* img, int format, int luma,
+                              int stride);
+/* erp_frontend_track on such a frame */
+int erp_frontend_track_warped(erp_frontend* f, erp_warp* w, const uint8_t* img, int format, int luma, int stride,
+                              int* n_features);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

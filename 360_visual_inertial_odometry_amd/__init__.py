@@ -27,6 +27,9 @@ VIO_INGEST_ROUTE_AUTO, VIO_INGEST_ROUTE_FUSED, VIO_INGEST_ROUTE_TWO_PASS, VIO_IN
 VIO_WARP_X_CONSTANT, VIO_WARP_X_WRAP = 0, 1
 VIO_WARP_Y_CONSTANT, VIO_WARP_Y_REPLICATE = 0, 2
 VIO_WARP_ROUTE_AUTO, VIO_WARP_ROUTE_SINGLE = 0, 1
+# contrast equalisation: modes and the horizontal border rule of CLAHE's tile interpolation
+VIO_EQ_NONE, VIO_EQ_HIST, VIO_EQ_CLAHE = 0, 1, 2
+VIO_EQ_X_CLAMP, VIO_EQ_X_WRAP = 0, 1
 
 EXPORTS = [
     "vio_abi_version", "vio_ctx_create", "vio_ctx_destroy", "vio_ctx_last_error",
@@ -51,6 +54,8 @@ EXPORTS = [
     "erp_warp_create", "erp_warp_destroy", "erp_warp_quantize", "erp_warp_check", "erp_warp_apply",
     "erp_warp_apply_device", "erp_warp_kernel_ms", "erp_warp_set_route", "erp_warp_map_erp",
     "erp_warp_map_fisheye", "erp_warp_map_cubemap", "erp_tracker_upload_warped", "erp_frontend_track_warped",
+    "erp_equalize_check", "erp_equalize_lut", "erp_equalize", "erp_equalize_device", "erp_equalize_kernel_ms",
+    "erp_equalize_set_stage_timing", "erp_equalize_stage_ms", "erp_tracker_equalize", "erp_frontend_set_equalize",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -161,6 +166,16 @@ def lib():
                                        C.c_int, vp, vp]
     L.erp_tracker_upload_warped.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int]
     L.erp_frontend_track_warped.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    eqp = C.POINTER(abi.ErpEqualizeParams)
+    L.erp_equalize_check.argtypes = [eqp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.erp_equalize_lut.argtypes = [C.c_int, vp, C.c_int, C.c_double, vp]
+    L.erp_equalize.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, eqp, vp, C.c_int]
+    L.erp_equalize_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, eqp, vp, C.c_int]
+    L.erp_equalize_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.erp_equalize_set_stage_timing.argtypes = [vp, C.c_int]
+    L.erp_equalize_stage_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 3
+    L.erp_tracker_equalize.argtypes = [vp, C.c_int, eqp]
+    L.erp_frontend_set_equalize.argtypes = [vp, eqp]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -438,6 +453,33 @@ class Context:
         sW x sH source frame; the maps' common row stride is honoured."""
         return Warp(self, map_x, map_y, sW, sH, border_x, border_y, border_value)
 
+    # ---- contrast equalisation ----
+    def equalize(self, img, params):
+        """erp_equalize: cv::equalizeHist / cv::CLAHE::apply of an (H, W) u8 frame (row stride honoured) by
+        `params` (equalize_params) -> (H, W) u8."""
+        a, W, H = _pix_rows(img, 1)
+        out = np.zeros((H, W), np.uint8)
+        self.check(lib().erp_equalize(self.h, _p(a), W, H, a.strides[0], C.byref(params), _p(out), W), "erp_equalize")
+        return out
+
+    def equalize_device(self, src_ptr, W, H, stride, n_frames, params, dst_ptr, dst_stride):
+        self.check(lib().erp_equalize_device(self.h, src_ptr, W, H, stride, n_frames, C.byref(params), dst_ptr,
+                                             dst_stride), "erp_equalize_device")
+
+    def equalize_kernel_ms(self):
+        ms = C.c_double()
+        self.check(lib().erp_equalize_kernel_ms(self.h, C.byref(ms)), "erp_equalize_kernel_ms")
+        return ms.value
+
+    def set_equalize_stage_timing(self, on):
+        """erp_equalize_set_stage_timing: later equalize launches record an event between their stages."""
+        self.check(lib().erp_equalize_set_stage_timing(self.h, 1 if on else 0), "erp_equalize_set_stage_timing")
+
+    def equalize_stage_ms(self):
+        v = [C.c_double() for _ in range(3)]
+        self.check(lib().erp_equalize_stage_ms(self.h, *[C.byref(x) for x in v]), "erp_equalize_stage_ms")
+        return dict(zip(["hist", "lut", "apply"], [x.value for x in v]))
+
     def resize_kernel_ms(self):
         ms = C.c_double()
         self.check(lib().erp_resize_area_kernel_ms(self.h, C.byref(ms)), "erp_resize_area_kernel_ms")
@@ -581,6 +623,30 @@ def warp_quantize(s, S, border_mode):
     if rc:
         raise VioError(f"erp_warp_quantize failed ({rc})")
     return q, valid
+
+
+def equalize_params(mode=VIO_EQ_CLAHE, tiles_x=8, tiles_y=8, clip_limit=3.0, border_x=VIO_EQ_X_CLAMP):
+    """erp_equalize_params; the defaults are cv::createCLAHE(3.0, Size(8, 8)) as VINS-style trackers run it."""
+    return abi.ErpEqualizeParams(int(mode), int(tiles_x), int(tiles_y), int(border_x), float(clip_limit))
+
+
+def equalize_check(params, W, H, stride=None, dst_stride=None):
+    """erp_equalize_check (host): the code erp_equalize* would return for these arguments."""
+    return lib().erp_equalize_check(C.byref(params), int(W), int(H), int(W if stride is None else stride),
+                                    int(W if dst_stride is None else dst_stride))
+
+
+def equalize_lut(mode, hist, area, clip_limit=0.0):
+    """erp_equalize_lut (host): the 256-entry LUT of one CLAHE tile of `area` pixels, or of a whole frame of `area`
+    pixels (VIO_EQ_HIST), from its 256-bin histogram."""
+    h = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if h.size != 256:
+        raise VioError("a histogram is 256 counts")
+    lut = np.zeros(256, np.uint8)
+    rc = lib().erp_equalize_lut(int(mode), _p(h), int(area), float(clip_limit), _p(lut))
+    if rc:
+        raise VioError(f"erp_equalize_lut failed ({rc})")
+    return lut
 
 
 def _rot9(R):
@@ -795,6 +861,10 @@ class Tracker:
         self.ctx.check(lib().erp_tracker_upload_warped(self.h, slot, warp.h, _p(a), int(fmt), int(luma), a.strides[0]),
                        "erp_tracker_upload_warped")
 
+    def equalize(self, slot, params):
+        """erp_tracker_equalize: equalise slot's frame in place (after an upload, before run); asynchronous."""
+        self.ctx.check(lib().erp_tracker_equalize(self.h, slot, C.byref(params)), "erp_tracker_equalize")
+
     def swap(self):
         self.ctx.check(lib().erp_tracker_swap(self.h), "erp_tracker_swap")
 
@@ -860,6 +930,11 @@ class Frontend:
         ctx.check(lib().erp_frontend_create(ctx.h, W, H, C.byref(self.params), C.byref(h)), "erp_frontend_create")
         self.h = h
         ctx._children.add(self)
+
+    def set_equalize(self, params=None):
+        """erp_frontend_set_equalize: equalise every later frame before tracking; None or VIO_EQ_NONE: off."""
+        self.ctx.check(lib().erp_frontend_set_equalize(self.h, C.byref(params) if params is not None else None),
+                       "erp_frontend_set_equalize")
 
     def track(self, img):
         img = _u8img(img)

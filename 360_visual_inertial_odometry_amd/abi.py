@@ -610,3 +610,9 @@ class ErpFisheyeLens(C.Structure):
 
 class ErpCubeFace(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+# ---- contrast equalisation (include/vio360.h) ----
+class ErpEqualizeParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("border_x", C.c_int32),
+                ("clip_limit", C.c_double)]

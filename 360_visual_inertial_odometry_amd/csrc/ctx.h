@@ -36,6 +36,11 @@ struct vio_ctx {
     int ba_route = VIO_BA_ROUTE_AUTO;
     // global-BA state kept between solves (ba_global_host.cpp GbaCache: look-ahead stream, captured graph)
     std::shared_ptr<void> gba_cache;
+    // equalisation: start / histograms done / LUTs done / end of the last erp_equalize_device (created on first use);
+    // the two inner events are recorded only under erp_equalize_set_stage_timing
+    hipEvent_t eq_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool eq_stage_timing = false;
+    bool eq_staged = false;  // the last launch recorded the inner events
 };
 
 namespace vio360 {
@@ -68,6 +73,8 @@ enum { kSlotGbaSolve = 20 };
 enum { kSlotResizeTabX = 21, kSlotResizeTabY = 22 };
 // erp_ingest_device, two-pass route: the grey camera-resolution plane between the convert and the resize
 enum { kSlotIngestPlane = 23 };
+// erp_equalize*: per-workgroup partial histograms, the tiles' LUTs, and the host entry point's frame
+enum { kSlotEqHist = 25, kSlotEqLut = 26, kSlotEqSrc = 27, kSlotEqDst = 28 };
 // pinned host slots: the one-shot solves' input image and every BA download's outputs image
 enum { kHostSlotBaIn = 0, kHostSlotBaOut = 1, kHostSlotGba = 2 };
 

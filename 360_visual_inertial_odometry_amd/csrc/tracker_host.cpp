@@ -630,6 +630,12 @@ int erp_tracker_upload_warped(erp_tracker* t, int slot, erp_warp* w, const uint8
     return erp_resize_area_any_device(ctx, d_warp, w->dW, w->dH, wp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
 }
 
+int erp_tracker_equalize(erp_tracker* t, int slot, const erp_equalize_params* p) {
+    if (!t || slot < 0 || slot > 1 || !p) return VIO_EINVAL;
+    if (p->mode == VIO_EQ_NONE) return erp_equalize_check(p, t->W, t->H, t->lp[0], t->lp[0]);
+    return erp_equalize_device(t->ctx, t->lvl[slot][0], t->W, t->H, t->lp[0], 1, p, t->lvl[slot][0], t->lp[0]);
+}
+
 int erp_tracker_device_frame(erp_tracker* t, int slot, uint8_t** dev_ptr, int* pitch) {
     if (!t || slot < 0 || slot > 1 || !dev_ptr || !pitch) return VIO_EINVAL;
     *dev_ptr = t->lvl[slot][0];
@@ -1046,6 +1052,7 @@ struct erp_frontend {
     int32_t next_id = 0;
     int num_tracked = 0, num_detected = 0;
     std::vector<FeatureRec> feats;
+    erp_equalize_params eq{};  // erp_frontend_set_equalize; mode VIO_EQ_NONE: off
 };
 
 namespace {
@@ -1119,6 +1126,7 @@ static int frontend_track_slot1(erp_frontend* f, int* n_features) {
     hipStream_t st = ctx->stream;
     int rc;
     const erp_frontend_params& P = f->p;
+    if (f->eq.mode != VIO_EQ_NONE && (rc = erp_tracker_equalize(t, 1, &f->eq))) return rc;
     if (f->frame == 0 || f->feats.empty()) {
         // first frame (or nothing to track): detect only (:68-97)
         f->feats.clear();
@@ -1225,6 +1233,18 @@ int erp_frontend_track_warped(erp_frontend* f, erp_warp* w, const uint8_t* img, 
     int rc;
     if ((rc = erp_tracker_upload_warped(f->t, 1, w, img, format, luma, stride))) return rc;
     return frontend_track_slot1(f, n_features);
+}
+
+int erp_frontend_set_equalize(erp_frontend* f, const erp_equalize_params* p) {
+    if (!f) return VIO_EINVAL;
+    if (!p || p->mode == VIO_EQ_NONE) {
+        f->eq = erp_equalize_params{};
+        return VIO_OK;
+    }
+    const int rc = erp_equalize_check(p, f->W, f->H, f->W, f->W);
+    if (rc) return rc;
+    f->eq = *p;
+    return VIO_OK;
 }
 
 int erp_frontend_features(erp_frontend* f, int32_t* ids, float* xy, int32_t* track_count, int32_t* age, int cap) {

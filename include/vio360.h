@@ -774,6 +774,69 @@ int erp_tracker_upload_warped(erp_tracker* t, int slot, erp_warp* w, const uint8
 int erp_frontend_track_warped(erp_frontend* f, erp_warp* w, const uint8_t* img, int format, int luma, int stride,
                               int* n_features);
 
+/* Contrast equalisation of a u8 frame on the device: cv::equalizeHist and cv::CLAHE::apply (8-bit) restated
+   (csrc/equalize.hip).  KLT front ends apply one of them to the frame before tracking; the reference
+   does not, so it is off unless asked for.  OpenCV is not available to this project: parity with it is unpinned,
+   as for the resize, the luma rules and the warp; the contract is this text and tests/equalize_oracle.py, which the
+   GPU matches bitwise.  All float arithmetic is float32, each operation rounded on its own (no FMA), division
+   correctly rounded; round() is round half to even, then a clamp to [0, 255].
+     VIO_EQ_HIST   hist[256] over the W x H frame, i0 its first non-empty bin.  hist[i0] == W H: every pixel is i0.
+                   Otherwise scale = 255.f / (float)(W H - hist[i0]), lut[i <= i0] = 0, and for i > i0:
+                   sum += hist[i], lut[i] = round((float)sum * scale); dst = lut[src].
+     VIO_EQ_CLAHE  tiling: tiles_x x tiles_y tiles over the frame if W % tiles_x == 0 and H % tiles_y == 0; else over
+                   the frame extended on the right by tiles_x - W % tiles_x columns and at the bottom by tiles_y -
+                   H % tiles_y rows with BORDER_REFLECT_101 (both axes as soon as one is not divisible: a divisible
+                   axis grows by a whole tiles count, as in OpenCV).  tw x th = extended size / tiles, area = tw th.
+                   LUT of a tile: its histogram; if clip_limit > 0: c = max((int)(clip_limit * area / 256), 1), the
+                   excess above c is cut from each bin and summed, batch = excess / 256, resid = excess - 256 batch,
+                   every bin += batch, and if resid > 0 the bins 0, step, 2 step, ... (step = max(256 / resid, 1))
+                   get +1 each while i < 256 and resid-- > 0; lut[i] = round((float)cumsum[i] * (255.f / (float)area)).
+                   Pixel (x, y) of the W x H frame, v = src: txf = (float)x * (1.f / (float)tw) - 0.5f, tx1 =
+                   floor(txf), tx2 = tx1 + 1, xa = txf - (float)tx1, xa1 = 1.f - xa, then tx1 = max(tx1, 0), tx2 =
+                   min(tx2, tiles_x - 1); y likewise; dst = round((L[ty1][tx1][v] * xa1 + L[ty1][tx2][v] * xa) * ya1 +
+                   (L[ty2][tx1][v] * xa1 + L[ty2][tx2][v] * xa) * ya), in that order.
+                   border_x = VIO_EQ_X_WRAP takes tx1 = -1 to tiles_x - 1 and tx2 = tiles_x to 0 instead: the mapping
+                   is continuous across the seam of a 360 degree frame.  It needs both axes divisible.
+   A call is valid if W, H >= 2, W H <= 2^30, stride and dst_stride >= W, the mode is known and, for CLAHE, 1 <=
+   tiles_x <= W / 2, 1 <= tiles_y <= H / 2 (one reflection suffices), clip_limit >= 0 and finite (0 = no clipping),
+   border_x known and WRAP only with both axes divisible; otherwise VIO_EINVAL.  VIO_EQ_NONE is a copy. */
+enum { VIO_EQ_NONE = 0, VIO_EQ_HIST = 1, VIO_EQ_CLAHE = 2 };
+enum { VIO_EQ_X_CLAMP = 0, VIO_EQ_X_WRAP = 1 };
+typedef struct {
+    int32_t mode;              /* VIO_EQ_* */
+    int32_t tiles_x, tiles_y;  /* CLAHE: tilesGridSize (8, 8) */
+    int32_t border_x;          /* CLAHE: VIO_EQ_X_* (CLAMP is OpenCV's behaviour) */
+    double clip_limit;         /* CLAHE: clipLimit (VINS-style trackers: 3.0) */
+} erp_equalize_params;
+/* host only: the argument check of erp_equalize* (one frame) without a context: VIO_OK, or VIO_EINVAL */
+int erp_equalize_check(const erp_equalize_params* p, int W, int H, int stride, int dst_stride);
+/* host only: the LUT rule of one tile of `area` pixels (CLAHE) or of a frame of `area` pixels (HIST; clip_limit is
+   ignored; a single-bin frame gives lut[i] = i0 for every i) from its 256-bin histogram */
+int erp_equalize_lut(int mode, const uint32_t* hist, int area, double clip_limit, uint8_t* lut);
+/* one W x H frame -> dst.  Blocking; host buffers. */
+int erp_equalize(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, const erp_equalize_params* p,
+                 uint8_t* dst, int dst_stride);
+/* the same for n_frames (at most 65535) DEVICE frames, laid out as erp_resize_area_any_device lays them out (frame f
+   at src + f*stride*H, dst + f*dst_stride*H), each equalised on its own, async on the context stream.  No alignment
+   is required of src, dst or the strides, and the padding of the destination rows is not written.  dst may be src
+   (with dst_stride == stride): the bytes are those of the out-of-place call; any other overlap is undefined.  More
+   tiles than one launch holds (2^21 workgroups) is VIO_ENOSYS. */
+int erp_equalize_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, int n_frames,
+                        const erp_equalize_params* p, uint8_t* dst, int dst_stride);
+/* device time (ms) of the last erp_equalize_device launches on this context, all three stages (waits for them) */
+int erp_equalize_kernel_ms(vio_ctx* ctx, double* ms);
+/* diagnostics (tools/equalize_time.py): on = later launches also record an event between the stages (each marker
+   costs the stream a few microseconds; off by default), and erp_equalize_stage_ms gives the last such launch's
+   histogram, LUT and apply times (VIO_EINVAL if it recorded none) */
+int erp_equalize_set_stage_timing(vio_ctx* ctx, int on);
+int erp_equalize_stage_ms(vio_ctx* ctx, double* hist_ms, double* lut_ms, double* apply_ms);
+/* equalise slot's frame in place, after any erp_tracker_upload* and before erp_tracker_run; asynchronous */
+int erp_tracker_equalize(erp_tracker* t, int slot, const erp_equalize_params* p);
+/* equalise every later frame of the front end before anything reads it, whichever erp_frontend_track* brings it
+   (upload, resize, luma, warp: all of them compose with it); p == NULL or VIO_EQ_NONE: off (the default; no kernel
+   is launched).  The parameters are checked against the front end's size: VIO_EINVAL leaves the setting as it was. */
+int erp_frontend_set_equalize(erp_frontend* f, const erp_equalize_params* p);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

@@ -11,13 +11,17 @@
  *   ValidateInitialization  :889-995,  ComputeReprojectionErrorInFrame :837-871;
  *   NormalizeScale          :997-1048.
  * The reference solves the null vectors / SVDs with Eigen's f32 JacobiSVD (Eigen is absent from the
- * image: parity with it is unpinned).  This restatement — like the device path — takes the null
+ * image: bit parity with it is not pinned).  This restatement — like the device path — takes the null
  * vector as the smallest-eigenvalue eigenvector of G = A^T A in f64 (cyclic Jacobi), with a fixed
  * sign, and the 3x3 SVDs through the eigen-decomposition of M^T M; the refit's sum over inliers is
  * restated in the fixed order the device uses (64 strided partial sums, then in lane order).  The
  * per-point f32 expressions are the reference's.  Pinned by closed forms in tests/test_init_oracle.py
  * (noise-free two-view geometry: E = [t]x R up to scale, exact R / t direction, zero epipolar
- * residuals, the four-candidate set).  Compile with -ffp-contract=off.
+ * residuals, the four-candidate set), and by tests/test_init_reference.py against an independent f64
+ * restatement of Initializer.cpp (tests/mono_init_reference.py: numpy SVDs of the f32-built systems
+ * themselves), which pins the exact null vector of those systems and every threshold, comparison and
+ * convention (strict <, W / W^T, R^T in the mid-point, even / odd median, no wrap-around of the pixel
+ * error, which inliers feed which stage).  Compile with -ffp-contract=off.
  */
 #include <math.h>
 #include <stdint.h>

@@ -1,7 +1,10 @@
 """CPU checks of the monocular initialiser (Initializer.cpp) — the oracle
 (oracle/init_oracle.c) against closed-form two-view geometry, and the host helpers of the C-ABI
 (sampler, SelectFeaturesForInit, ComputeParallax, pose composition) against Python restatements.
-Parity with Eigen's f32 JacobiSVD is unpinned (Eigen is absent from the image)."""
+tests/test_init_reference.py holds the same oracle to an independent f64 restatement of Initializer.cpp
+(tests/mono_init_reference.py): that pins the exact null vector of the f32-built system and every
+threshold, comparison and convention.  Still not pinned: bit parity with Eigen's f32 JacobiSVD (Eigen is
+absent from the image)."""
 import numpy as np
 import pytest
 

@@ -30,6 +30,8 @@ VIO_WARP_ROUTE_AUTO, VIO_WARP_ROUTE_SINGLE = 0, 1
 # contrast equalisation: modes and the horizontal border rule of CLAHE's tile interpolation
 VIO_EQ_NONE, VIO_EQ_HIST, VIO_EQ_CLAHE = 0, 1, 2
 VIO_EQ_X_CLAMP, VIO_EQ_X_WRAP = 0, 1
+# region masks: the horizontal border rule of the erosion
+VIO_MASK_X_CLAMP, VIO_MASK_X_WRAP = 0, 1
 
 EXPORTS = [
     "vio_abi_version", "vio_ctx_create", "vio_ctx_destroy", "vio_ctx_last_error",
@@ -56,6 +58,9 @@ EXPORTS = [
     "erp_warp_map_fisheye", "erp_warp_map_cubemap", "erp_tracker_upload_warped", "erp_frontend_track_warped",
     "erp_equalize_check", "erp_equalize_lut", "erp_equalize", "erp_equalize_device", "erp_equalize_kernel_ms",
     "erp_equalize_set_stage_timing", "erp_equalize_stage_ms", "erp_tracker_equalize", "erp_frontend_set_equalize",
+    "erp_mask_check", "erp_mask_build", "erp_mask_build_device", "erp_mask_build_warped", "erp_mask_kernel_ms",
+    "erp_tracker_set_mask", "erp_tracker_set_mask_device", "erp_tracker_set_mask_warped", "erp_tracker_get_mask",
+    "erp_frontend_set_mask", "erp_frontend_set_mask_device", "erp_frontend_set_mask_warped",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -176,6 +181,19 @@ def lib():
     L.erp_equalize_stage_ms.argtypes = [vp] + [C.POINTER(C.c_double)] * 3
     L.erp_tracker_equalize.argtypes = [vp, C.c_int, eqp]
     L.erp_frontend_set_equalize.argtypes = [vp, eqp]
+    if hasattr(L, "erp_mask_check") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        mkp = C.POINTER(abi.ErpMaskParams)
+        L.erp_mask_check.argtypes = [C.c_int] * 6 + [mkp]
+        L.erp_mask_build.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, mkp, vp, C.c_int]
+        L.erp_mask_build_device.argtypes = L.erp_mask_build.argtypes
+        L.erp_mask_build_warped.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, mkp, vp, C.c_int]
+        L.erp_mask_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        for name in ("erp_tracker_set_mask", "erp_tracker_set_mask_device", "erp_frontend_set_mask",
+                     "erp_frontend_set_mask_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, mkp]
+        L.erp_tracker_set_mask_warped.argtypes = [vp, vp, vp, C.c_int, mkp]
+        L.erp_frontend_set_mask_warped.argtypes = [vp, vp, vp, C.c_int, mkp]
+        L.erp_tracker_get_mask.argtypes = [vp, vp, C.c_int]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -480,6 +498,25 @@ class Context:
         self.check(lib().erp_equalize_stage_ms(self.h, *[C.byref(x) for x in v]), "erp_equalize_stage_ms")
         return dict(zip(["hist", "lut", "apply"], [x.value for x in v]))
 
+    # ---- region masks ----
+    def mask_build(self, mask, dW, dH, params=None):
+        """erp_mask_build: an (sH, sW) u8 usable-region mask (nonzero = usable, row stride honoured), reduced
+        conservatively to (dW, dH) and eroded by `params` (mask_params) -> (dH, dW) u8 of 0 / 255."""
+        a, W, H = _pix_rows(mask, 1)
+        out = np.zeros((dH, dW), np.uint8)
+        self.check(lib().erp_mask_build(self.h, _p(a), W, H, a.strides[0], int(dW), int(dH),
+                                        C.byref(params or mask_params()), _p(out), dW), "erp_mask_build")
+        return out
+
+    def mask_build_device(self, src_ptr, sW, sH, stride, dW, dH, params, dst_ptr, dst_stride):
+        self.check(lib().erp_mask_build_device(self.h, src_ptr, sW, sH, stride, dW, dH, C.byref(params), dst_ptr,
+                                               dst_stride), "erp_mask_build_device")
+
+    def mask_kernel_ms(self):
+        ms = C.c_double()
+        self.check(lib().erp_mask_kernel_ms(self.h, C.byref(ms)), "erp_mask_kernel_ms")
+        return ms.value
+
     def resize_kernel_ms(self):
         ms = C.c_double()
         self.check(lib().erp_resize_area_kernel_ms(self.h, C.byref(ms)), "erp_resize_area_kernel_ms")
@@ -628,6 +665,37 @@ def warp_quantize(s, S, border_mode):
 def equalize_params(mode=VIO_EQ_CLAHE, tiles_x=8, tiles_y=8, clip_limit=3.0, border_x=VIO_EQ_X_CLAMP):
     """erp_equalize_params; the defaults are cv::createCLAHE(3.0, Size(8, 8)) as VINS-style trackers run it."""
     return abi.ErpEqualizeParams(int(mode), int(tiles_x), int(tiles_y), int(border_x), float(clip_limit))
+
+
+def mask_params(erode_radius=0, border_x=VIO_MASK_X_CLAMP):
+    """erp_mask_params: the erosion radius in tracker pixels and its horizontal border rule (VIO_MASK_X_*)."""
+    return abi.ErpMaskParams(int(erode_radius), int(border_x))
+
+
+def mask_check(sW, sH, dW, dH, params, stride=None, dst_stride=None):
+    """erp_mask_check (host): the code erp_mask_build* would return for these arguments."""
+    return lib().erp_mask_check(int(sW), int(sH), int(sW if stride is None else stride), int(dW), int(dH),
+                                int(dW if dst_stride is None else dst_stride),
+                                C.byref(params) if params is not None else None)
+
+
+def _set_mask(owner, name, mask, params):
+    """erp_{tracker,frontend}_set_mask: an (H, W) u8 host mask, or None to clear"""
+    fn = getattr(lib(), name)
+    if mask is None:
+        owner.ctx.check(fn(owner.h, None, 0, 0, 0, None), name)
+        return
+    a, W, H = _pix_rows(mask, 1)
+    owner.ctx.check(fn(owner.h, _p(a), W, H, a.strides[0], C.byref(params or mask_params())), name)
+
+
+def _set_mask_warped(owner, name, warp, src_mask, params):
+    a, stride = None, 0
+    if src_mask is not None:
+        a = warp._frame(src_mask, VIO_PIX_GRAY8)
+        stride = a.strides[0]
+    owner.ctx.check(getattr(lib(), name)(owner.h, warp.h, None if a is None else _p(a), stride,
+                                         C.byref(params or mask_params())), name)
 
 
 def equalize_check(params, W, H, stride=None, dst_stride=None):
@@ -800,6 +868,21 @@ class Warp:
         self.ctx.check(lib().erp_warp_apply_device(self.h, src_ptr, int(fmt), int(luma), stride, n_frames, dst_ptr,
                                                    dst_stride), "erp_warp_apply_device")
 
+    def mask_build(self, src_mask, dW=None, dH=None, params=None):
+        """erp_mask_build_warped: the usable pixels of the warp's destination for a source-space mask ((sH, sW) u8,
+        nonzero = usable, or None: every source pixel), reduced to (dW, dH) (default: the warp's size) and eroded
+        -> (dH, dW) u8 of 0 / 255."""
+        dW, dH = int(self.dW if dW is None else dW), int(self.dH if dH is None else dH)
+        a, stride = None, 0
+        if src_mask is not None:
+            a = self._frame(src_mask, VIO_PIX_GRAY8)
+            stride = a.strides[0]
+        out = np.zeros((dH, dW), np.uint8)
+        self.ctx.check(lib().erp_mask_build_warped(self.h, None if a is None else _p(a), stride, dW, dH,
+                                                   C.byref(params or mask_params()), _p(out), dW),
+                       "erp_mask_build_warped")
+        return out
+
     def check(self, fmt, luma, stride, dst_stride):
         """erp_warp_check (host): the code erp_warp_apply* would return for these arguments."""
         return lib().erp_warp_check(self.h, int(fmt), int(luma), int(stride), int(dst_stride))
@@ -864,6 +947,27 @@ class Tracker:
     def equalize(self, slot, params):
         """erp_tracker_equalize: equalise slot's frame in place (after an upload, before run); asynchronous."""
         self.ctx.check(lib().erp_tracker_equalize(self.h, slot, C.byref(params)), "erp_tracker_equalize")
+
+    def set_mask(self, mask, params=None):
+        """erp_tracker_set_mask: a usable-region mask ((H, W) u8, nonzero = usable) at the tracker's or the
+        camera's size, eroded by `params` (mask_params); None clears it."""
+        _set_mask(self, "erp_tracker_set_mask", mask, params)
+
+    def set_mask_device(self, ptr, W, H, stride, params=None):
+        """erp_tracker_set_mask_device: the same from a device mask, asynchronous (no host synchronisation)."""
+        self.ctx.check(lib().erp_tracker_set_mask_device(self.h, ptr, W, H, stride, C.byref(params or mask_params())),
+                       "erp_tracker_set_mask_device")
+
+    def set_mask_warped(self, warp, src_mask=None, params=None):
+        """erp_tracker_set_mask_warped: the usable region of `warp`'s destination (src_mask: (sH, sW) u8 in the
+        warp's source coordinates, or None), the mask that goes with upload_warped."""
+        _set_mask_warped(self, "erp_tracker_set_mask_warped", warp, src_mask, params)
+
+    def get_mask(self):
+        """erp_tracker_get_mask: the mask in use as (H, W) u8 of 0 / 255; all 255 when none is set."""
+        out = np.zeros((self.H, self.W), np.uint8)
+        self.ctx.check(lib().erp_tracker_get_mask(self.h, _p(out), self.W), "erp_tracker_get_mask")
+        return out
 
     def swap(self):
         self.ctx.check(lib().erp_tracker_swap(self.h), "erp_tracker_swap")
@@ -935,6 +1039,20 @@ class Frontend:
         """erp_frontend_set_equalize: equalise every later frame before tracking; None or VIO_EQ_NONE: off."""
         self.ctx.check(lib().erp_frontend_set_equalize(self.h, C.byref(params) if params is not None else None),
                        "erp_frontend_set_equalize")
+
+    def set_mask(self, mask, params=None):
+        """erp_frontend_set_mask: a usable-region mask for every later frame (detection and the tracked-point
+        filter); None clears it."""
+        _set_mask(self, "erp_frontend_set_mask", mask, params)
+
+    def set_mask_device(self, ptr, W, H, stride, params=None):
+        """erp_frontend_set_mask_device: the same from a device mask, asynchronous."""
+        self.ctx.check(lib().erp_frontend_set_mask_device(self.h, ptr, W, H, stride, C.byref(params or mask_params())),
+                       "erp_frontend_set_mask_device")
+
+    def set_mask_warped(self, warp, src_mask=None, params=None):
+        """erp_frontend_set_mask_warped: the usable region of `warp`'s destination, for track_warped."""
+        _set_mask_warped(self, "erp_frontend_set_mask_warped", warp, src_mask, params)
 
     def track(self, img):
         img = _u8img(img)

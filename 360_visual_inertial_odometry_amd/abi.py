@@ -616,3 +616,8 @@ class ErpCubeFace(C.Structure):
 class ErpEqualizeParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("border_x", C.c_int32),
                 ("clip_limit", C.c_double)]
+
+
+# ---- region masks (include/vio360.h) ----
+class ErpMaskParams(C.Structure):
+    _fields_ = [("erode_radius", C.c_int32), ("border_x", C.c_int32)]

@@ -801,6 +801,8 @@ void vio_ctx_destroy(vio_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->eq_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->mask_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

@@ -41,6 +41,10 @@ struct vio_ctx {
     hipEvent_t eq_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool eq_stage_timing = false;
     bool eq_staged = false;  // the last launch recorded the inner events
+    // region masks: start / end of the last build's launches (created on first use), and the (sW, dW, sH, dH) of the
+    // footprint tables now in kSlotMaskTab
+    hipEvent_t mask_ev[2] = {nullptr, nullptr};
+    int mask_tab_key[4] = {0, 0, 0, 0};
 };
 
 namespace vio360 {
@@ -75,6 +79,7 @@ enum { kSlotResizeTabX = 21, kSlotResizeTabY = 22 };
 enum { kSlotIngestPlane = 23 };
 // erp_equalize*: per-workgroup partial histograms, the tiles' LUTs, and the host entry point's frame
 enum { kSlotEqHist = 25, kSlotEqLut = 26, kSlotEqSrc = 27, kSlotEqDst = 28 };
+// (slots 29 to 33: the region-mask builds, mask.h)
 // pinned host slots: the one-shot solves' input image and every BA download's outputs image
 enum { kHostSlotBaIn = 0, kHostSlotBaOut = 1, kHostSlotGba = 2 };
 

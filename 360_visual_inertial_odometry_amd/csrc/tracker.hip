@@ -54,8 +54,13 @@ __device__ __forceinline__ int reflect101(int p, int n) {
     return p;
 }
 
+// MASKED: G.static_bits (a region mask's exclusion plane) is part of the static region (pass 1 with a mask set; the
+// maskless instance is the code it was before masks existed)
+template <bool MASKED = false>
 __device__ __forceinline__ bool lm_static_in(const GfArgs& G, int x, int y) {
-    return y >= G.top_rows && y < G.bottom_start && x >= G.margin && x < G.W - G.margin;
+    const bool in = y >= G.top_rows && y < G.bottom_start && x >= G.margin && x < G.W - G.margin;
+    if constexpr (MASKED) return in && !((G.static_bits[(size_t)y * G.disc_words + (x >> 5)] >> (x & 31)) & 1u);
+    else return in;
 }
 __device__ __forceinline__ bool lm_disc(const GfArgs& G, int x, int y) {
     return G.disc_bits && ((G.disc_bits[(size_t)y * G.disc_words + (x >> 5)] >> (x & 31)) & 1u);
@@ -259,8 +264,14 @@ __device__ void lk_aux(const LkAux& X, int b) {
     if (X.disc) {
         const size_t n4 = X.disc_words / 4;
         uint4* d4p = reinterpret_cast<uint4*>(X.disc);
-        for (size_t i = t; i < n4; i += stride) d4p[i] = make_uint4(0u, 0u, 0u, 0u);
-        for (size_t i = 4 * n4 + t; i < X.disc_words; i += stride) X.disc[i] = 0u;
+        if (X.disc_src) {  // a region mask is set: the discs are stamped onto its exclusion plane
+            const uint4* s4p = reinterpret_cast<const uint4*>(X.disc_src);
+            for (size_t i = t; i < n4; i += stride) d4p[i] = s4p[i];
+            for (size_t i = 4 * n4 + t; i < X.disc_words; i += stride) X.disc[i] = X.disc_src[i];
+        } else {
+            for (size_t i = t; i < n4; i += stride) d4p[i] = make_uint4(0u, 0u, 0u, 0u);
+            for (size_t i = 4 * n4 + t; i < X.disc_words; i += stride) X.disc[i] = 0u;
+        }
     }
 }
 
@@ -483,6 +494,11 @@ __device__ int ransac_prep_body(const RansacArgs& R, int* wsum, int& base) {
                 float m = (float)R.margin;
                 bool nearb = (x < m) || (x > (float)R.W - m) || (y < m) || (y > (float)R.H - m);
                 good = R.status[i] && !polar && !nearb;
+                if (R.excl_bits && good) {  // region mask: the pixel the point rounds to (as the disc centres)
+                    const int xi = (int)rintf(x), yi = (int)rintf(y);
+                    good = (unsigned)xi < (unsigned)R.W && (unsigned)yi < (unsigned)R.H &&
+                           !((R.excl_bits[(size_t)yi * R.excl_words + (xi >> 5)] >> (xi & 31)) & 1u);
+                }
             }
             R.kept[i] = 0;
         }
@@ -1946,6 +1962,7 @@ __device__ __forceinline__ uint32_t lm_block_max(uint32_t m, uint32_t* red) {
 }
 
 // pass 1: per tile, the 3x3 local maxima inside the static region and the region's maximum
+template <bool MASKED>
 __global__ void __launch_bounds__(256) gftt_lmax_kernel(GfArgs G) {
     __shared__ LmShared<LM_TY> S;
     // the tile's local maxima over the derivative planes (dead once the eigenvalues are formed): 4 workgroups per CU
@@ -1973,7 +1990,7 @@ __global__ void __launch_bounds__(256) gftt_lmax_kernel(GfArgs G) {
         const int Y = oy + ty;
         bool c = false;
         float v = 0.f;
-        if (X < G.W && Y < G.H && lm_static_in(G, X, Y)) {
+        if (X < G.W && Y < G.H && lm_static_in<MASKED>(G, X, Y)) {
             v = S.eig[ty + 1][tx + 1];
             m = max(m, ord_f32(v));
             c = v > 0.f && X >= 1 && X < G.W - 1 && Y >= 1 && Y < G.H - 1 && !(fmaxf(fmaxf(hm0, hm1), hm2) > v);
@@ -2387,7 +2404,8 @@ hipError_t launch_gftt(const GfArgs& g, void* sort_tmp, size_t sort_tmp_bytes, h
     return launch_select(g, (const unsigned long long*)g.topk_sorted, (const unsigned int*)g.n_top, g.topk_cap, 1, st);
 }
 hipError_t launch_gftt_lmax(const GfArgs& g, hipStream_t st) {
-    hipLaunchKernelGGL(gftt_lmax_kernel, dim3(g.tiles_x * g.tiles_y), dim3(256), 0, st, g);
+    if (g.static_bits) hipLaunchKernelGGL(gftt_lmax_kernel<true>, dim3(g.tiles_x * g.tiles_y), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(gftt_lmax_kernel<false>, dim3(g.tiles_x * g.tiles_y), dim3(256), 0, st, g);
     return hipGetLastError();
 }
 // after pass 1 and the disc mask: masked maximum (clean tiles, then the touched tiles that could

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "mask.h"
 #include "tracker_types.h"
 #include "warp.h"
 
@@ -82,6 +83,11 @@ struct erp_tracker {
     int* d_halfw = nullptr;
     int halfw_r = -1;
     uint8_t* d_mask = nullptr;  // explicit mask (erp_gftt)
+    // region mask (erp_tracker_set_mask*): its exclusion plane in the disc plane's layout, what the disc plane
+    // starts from and what the tracked-point filter tests; d_usable: the front end's per-point flags
+    uint32_t* d_static = nullptr;
+    bool has_mask = false;
+    uint8_t* d_usable = nullptr;
     // GFTT top-K fast path
     unsigned int* d_hist = nullptr;
     unsigned long long *d_topk = nullptr, *d_topk_sorted = nullptr;
@@ -317,6 +323,8 @@ RansacArgs ransac_args(erp_tracker* t, int n, int mode, int iters, uint32_t seed
     r.p0 = p0; r.p1 = p1; r.status = t->d_status;
     r.n = n; r.W = t->W; r.H = t->H; r.mode = mode;
     r.polar_ratio = polar; r.margin = margin;
+    r.excl_bits = mode == 1 && t->has_mask ? t->d_static : nullptr;
+    r.excl_words = t->disc_words;
     r.gidx = t->d_gidx; r.n_good = t->d_scal + 0;
     r.b0 = t->d_b0; r.b1 = t->d_b1;
     r.samples = t->d_samples; r.iters = iters; r.seed = seed; r.thresh = thr;
@@ -347,6 +355,10 @@ GfArgs gf_lmax_args(erp_tracker* t, const uint8_t* img, int pitch, int margin, f
     g.img = img; g.W = t->W; g.H = t->H; g.pitch = pitch;
     gf_static_region(t, margin, polar, g);
     gf_lmax_fields(t, g);
+    // a region mask is part of pass 1's static region: a large mask then neither fills the presort's prefix with
+    // keys the greedy pass has to skip nor raises the tile maxima the threshold is bounded by
+    g.static_bits = t->has_mask ? t->d_static : nullptr;
+    g.disc_words = t->disc_words;
     return g;
 }
 
@@ -385,7 +397,8 @@ int enqueue_gftt(erp_tracker* t, const uint8_t* img, int pitch, const uint8_t* m
     g.mask = mask; g.mask_pitch = mask_pitch;
     gf_static_region(t, margin, polar, g);
     if (!mask) gf_lmax_fields(t, g);  // analytic mask: the local-maximum path
-    g.disc_bits = discs ? t->d_disc : nullptr;
+    // the exclusion plane: the discs stamped onto the region mask's plane, the mask's plane alone, or none
+    g.disc_bits = discs ? t->d_disc : (t->has_mask ? t->d_static : nullptr);
     g.disc_words = t->disc_words;
     g.quality = quality; g.min_dist = min_dist; g.max_corners = max_corners;
     g.max_ord = (uint32_t*)(t->d_scal + 2);
@@ -726,6 +739,7 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
         x.scal = t->d_scal;
         x.disc = t->d_disc;
         x.disc_words = (size_t)t->disc_words * t->H;
+        x.disc_src = t->has_mask ? t->d_static : nullptr;
         x.pts = t->d_pts;
         x.bear0 = t->d_bear0;
         x.n = n;
@@ -1069,7 +1083,9 @@ int frontend_detect(erp_frontend* f, std::vector<float>& corners) {
         std::vector<float> xy(2 * (size_t)n);
         for (int i = 0; i < n; ++i) { xy[2 * i] = f->feats[i].x; xy[2 * i + 1] = f->feats[i].y; }
         VIO_HIP(t->ctx, hipMemcpyAsync(t->d_pts, xy.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
-        VIO_HIP(t->ctx, hipMemsetAsync(t->d_disc, 0, sizeof(uint32_t) * t->disc_words * t->H, st));
+        const size_t disc_bytes = sizeof(uint32_t) * t->disc_words * t->H;
+        if (t->has_mask) VIO_HIP(t->ctx, hipMemcpyAsync(t->d_disc, t->d_static, disc_bytes, hipMemcpyDeviceToDevice, st));
+        else VIO_HIP(t->ctx, hipMemsetAsync(t->d_disc, 0, disc_bytes, st));
         const int radius = (int)f->p.min_distance;
         if (radius != t->halfw_r) {
             std::vector<int> hw = circle_half_widths(radius);
@@ -1141,13 +1157,18 @@ static int frontend_track_slot1(erp_frontend* f, int* n_features) {
         const int n = (int)f->feats.size();
         if (n > t->max_points) { set_error(ctx, "too many features"); return VIO_ENOSYS; }
         std::vector<float> prev(2 * (size_t)n), next(2 * (size_t)n);
-        std::vector<uint8_t> status(n);
+        std::vector<uint8_t> status(n), usable;
         for (int i = 0; i < n; ++i) { prev[2 * i] = f->feats[i].x; prev[2 * i + 1] = f->feats[i].y; }
         if ((rc = erp_tracker_set_points(t, prev.data(), n))) return rc;
         erp_klt_params kp{21, 3, 30, 0.01f, 0.01f, 0};  // FeatureTracker.cpp:33-35, 240
         if ((rc = enqueue_lk(t, &kp, n))) return rc;
         VIO_HIP(ctx, hipMemcpyAsync(next.data(), t->d_next, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
         VIO_HIP(ctx, hipMemcpyAsync(status.data(), t->d_status, n, hipMemcpyDeviceToHost, st));
+        if (t->has_mask) {  // the region mask's bit under every tracked point, gathered on the device
+            usable.resize(n);
+            VIO_HIP(ctx, launch_mask_gather(t->d_next, n, t->d_static, t->W, t->H, t->d_usable, st));
+            VIO_HIP(ctx, hipMemcpyAsync(usable.data(), t->d_usable, n, hipMemcpyDeviceToHost, st));
+        }
         VIO_HIP(ctx, hipStreamSynchronize(st));
         // status ∧ !IsInPolarRegion ∧ !IsNearBoundary (:117-126; Camera.cpp:120-139)
         std::vector<int> good;
@@ -1157,7 +1178,7 @@ static int frontend_track_slot1(erp_frontend* f, int* n_features) {
             float vr = y / (float)f->H;
             bool polar = vr < 0.15f || vr > (1.0f - 0.15f);
             bool nearb = x < m || x > (float)f->W - m || y < m || y > (float)f->H - m;
-            if (status[i] && !polar && !nearb) good.push_back(i);
+            if (status[i] && !polar && !nearb && (usable.empty() || usable[i])) good.push_back(i);
         }
         std::vector<uint8_t> inl(good.size(), 1);
         if (good.size() >= 3) {  // RejectOutliersRotationRANSAC (:253-328)
@@ -1245,6 +1266,129 @@ int erp_frontend_set_equalize(erp_frontend* f, const erp_equalize_params* p) {
     if (rc) return rc;
     f->eq = *p;
     return VIO_OK;
+}
+
+// ---- region masks (mask.h; the kernels in mask.hip) ----
+
+// the enqueued build replaces the tracker's plane: a captured run would replay the old arguments
+static void mask_changed(erp_tracker* t, bool has_mask) {
+    t->has_mask = has_mask;
+    if (t->run_graph) {
+        (void)hipGraphExecDestroy(t->run_graph);
+        t->run_graph = nullptr;
+    }
+}
+
+// d_src: a DEVICE mask (W x H), or with a warp its source-space mask or null
+static int tracker_build_mask(erp_tracker* t, const uint8_t* d_src, int W, int H, long long stride, erp_warp* w,
+                              const erp_mask_params* p) {
+    int rc;
+    if (!t->d_static) {
+        if ((rc = dalloc(t, &t->d_static, sizeof(uint32_t) * t->disc_words * t->H))) return rc;
+        if ((rc = dalloc(t, &t->d_usable, std::max(t->max_points, 1)))) return rc;
+    }
+    if ((rc = mask_enqueue(t->ctx, d_src, W, H, stride, w, t->W, t->H, p, t->d_static))) return rc;
+    mask_changed(t, true);
+    return VIO_OK;
+}
+
+int erp_tracker_set_mask_device(erp_tracker* t, const uint8_t* dmask, int W, int H, int stride,
+                                const erp_mask_params* p) {
+    if (!t) return VIO_EINVAL;
+    if (!dmask) {
+        mask_changed(t, false);
+        return VIO_OK;
+    }
+    const int rc = erp_mask_check(W, H, stride, t->W, t->H, t->W, p);
+    if (rc) {
+        set_error(t->ctx, "erp_tracker_set_mask: bad sizes, stride, radius or border mode, or a mask smaller than the frame");
+        return rc;
+    }
+    VIO_DEVICE(t->ctx);
+    return tracker_build_mask(t, dmask, W, H, stride, nullptr, p);
+}
+
+int erp_tracker_set_mask(erp_tracker* t, const uint8_t* mask, int W, int H, int stride, const erp_mask_params* p) {
+    if (!t) return VIO_EINVAL;
+    if (!mask) {
+        mask_changed(t, false);
+        return VIO_OK;
+    }
+    const int rc = erp_mask_check(W, H, stride, t->W, t->H, t->W, p);
+    if (rc) {
+        set_error(t->ctx, "erp_tracker_set_mask: bad sizes, stride, radius or border mode, or a mask smaller than the frame");
+        return rc;
+    }
+    vio_ctx* ctx = t->ctx;
+    VIO_DEVICE(ctx);
+    const int sp = (W + 15) & ~15;
+    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskSrc, (size_t)sp * H));
+    if (!d_src) {
+        set_error(ctx, "erp_tracker_set_mask: device allocation failed");
+        return VIO_ENOMEM;
+    }
+    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    return tracker_build_mask(t, d_src, W, H, sp, nullptr, p);
+}
+
+int erp_tracker_set_mask_warped(erp_tracker* t, erp_warp* w, const uint8_t* src_mask, int stride,
+                                const erp_mask_params* p) {
+    if (!t || !w) return VIO_EINVAL;
+    vio_ctx* ctx = t->ctx;
+    if (w->ctx != ctx) {
+        set_error(ctx, "erp_tracker_set_mask_warped: the warp belongs to another context");
+        return VIO_EINVAL;
+    }
+    const int rc = mask_warp_check(w, src_mask, stride, t->W, t->H, p);
+    if (rc) {
+        set_error(ctx, "erp_tracker_set_mask_warped: bad stride, radius or border mode, or a warp smaller than the frame");
+        return rc;
+    }
+    VIO_DEVICE(ctx);
+    uint8_t* d_src = nullptr;
+    const int sp = (w->sW + 15) & ~15;
+    if (src_mask) {
+        d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskSrc, (size_t)sp * w->sH));
+        if (!d_src) {
+            set_error(ctx, "erp_tracker_set_mask_warped: device allocation failed");
+            return VIO_ENOMEM;
+        }
+        VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, src_mask, stride, w->sW, w->sH, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return tracker_build_mask(t, d_src, w->sW, w->sH, sp, w, p);
+}
+
+int erp_tracker_get_mask(erp_tracker* t, uint8_t* out, int stride) {
+    if (!t || !out || stride < t->W) return VIO_EINVAL;
+    if (!t->has_mask) {
+        for (int y = 0; y < t->H; ++y) std::memset(out + (size_t)y * stride, 255, t->W);
+        return VIO_OK;
+    }
+    vio_ctx* ctx = t->ctx;
+    VIO_DEVICE(ctx);
+    uint8_t* d_img = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskDst, (size_t)t->W * t->H));
+    if (!d_img) {
+        set_error(ctx, "erp_tracker_get_mask: device allocation failed");
+        return VIO_ENOMEM;
+    }
+    VIO_HIP(ctx, launch_mask_unpack(t->d_static, t->W, t->H, d_img, t->W, ctx->stream));
+    VIO_HIP(ctx, hipMemcpy2DAsync(out, stride, d_img, t->W, t->W, t->H, hipMemcpyDeviceToHost, ctx->stream));
+    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VIO_OK;
+}
+
+int erp_frontend_set_mask(erp_frontend* f, const uint8_t* mask, int W, int H, int stride, const erp_mask_params* p) {
+    return f ? erp_tracker_set_mask(f->t, mask, W, H, stride, p) : VIO_EINVAL;
+}
+
+int erp_frontend_set_mask_device(erp_frontend* f, const uint8_t* dmask, int W, int H, int stride,
+                                 const erp_mask_params* p) {
+    return f ? erp_tracker_set_mask_device(f->t, dmask, W, H, stride, p) : VIO_EINVAL;
+}
+
+int erp_frontend_set_mask_warped(erp_frontend* f, erp_warp* w, const uint8_t* src_mask, int stride,
+                                 const erp_mask_params* p) {
+    return f ? erp_tracker_set_mask_warped(f->t, w, src_mask, stride, p) : VIO_EINVAL;
 }
 
 int erp_frontend_features(erp_frontend* f, int32_t* ids, float* xy, int32_t* track_count, int32_t* age, int cap) {

@@ -40,6 +40,8 @@ struct RansacArgs {
     int n, W, H, mode;     // mode 0: every point enters RANSAC; 1: status/polar/boundary filter first
     float polar_ratio;
     int margin;
+    const uint32_t* excl_bits;  // mode 1: the region mask's exclusion plane (disc-plane layout), or null (no mask)
+    int excl_words;             // its 32-bit words per row
     int* gidx;             // [n] compacted -> input index
     int* n_good;           // device scalar
     float* b0;             // [n][3] bearings of the compacted points
@@ -67,6 +69,10 @@ struct GfArgs {
     int top_rows, bottom_start, margin;
     const uint32_t* disc_bits;
     int disc_words;  // 32-bit words per row
+    // pass 1 only (gftt_lmax_kernel): the region mask's exclusion plane, part of the static region there, so that the
+    // tile maxima, the local maxima and the presort's prefix already leave the mask out (null: no mask; the tail
+    // finds the same bits in disc_bits)
+    const uint32_t* static_bits;
     double quality, min_dist;
     int max_corners;
     uint32_t* max_ord;              // device scalar (ordered-int max of the masked eig map)
@@ -154,6 +160,7 @@ struct LkAux {
     int* scal;
     uint32_t* disc;
     size_t disc_words;  // total 32-bit words of the bitmap
+    const uint32_t* disc_src;  // the region mask's exclusion plane: the bitmap starts as its copy (null: zeros)
     const float* pts;   // the previous points' bearings (RANSAC's input) into bear0 [n][3] (null: none)
     float* bear0;
     int n, W, H;

@@ -837,6 +837,81 @@ int erp_tracker_equalize(erp_tracker* t, int slot, const erp_equalize_params* p)
    is launched).  The parameters are checked against the front end's size: VIO_EINVAL leaves the setting as it was. */
 int erp_frontend_set_equalize(erp_frontend* f, const erp_equalize_params* p);
 
+/* Region masks (csrc/mask.hip): which pixels of a 360 degree frame are not the scene -- the operator,
+   the rig, the holes of a dual-fisheye warp, the objects a segmentation network marks per frame.  A usable-region
+   mask is a u8 image, nonzero = usable (OpenCV's convention, that of erp_gftt's mask), given at the tracker's size,
+   at the camera's, or in the source coordinates of an erp_warp.  It is reduced conservatively to the tracker's size
+   on the device, optionally eroded, and held by a tracker or front end as a static exclusion plane.  The reference
+   has the hook (FeatureTracker.cpp:47-58 builds m_mask, :117-126 filters) and nothing to put into it.  Everything
+   is integer; the contract is this text and tests/mask_oracle.py, which the GPU matches bit for bit.
+     reduce   sW x sH -> dW x dH, dW <= sW and dH <= sH (enlarging on either axis: VIO_ENOSYS).  Per axis the
+              footprint of destination index d is the set of source indices si with an entry (d, si, alpha) in
+              erp_resize_area_tab(ssize, dsize): the taps the frame's own INTER_AREA resize reads.  A destination
+              pixel is usable iff every source pixel of footprint_x x footprint_y is nonzero: a tracker pixel that
+              contains any excluded camera pixel is excluded.  Equal sizes: the identity.
+     erode    radius r in [0, 255], in tracker pixels: usable'(x, y) = AND of usable(x + dx, y + dy) over |dx|,
+              |dy| <= r.  Rows outside the image count as usable (cv::erode's default border: the image edge does not
+              erode); columns outside count as usable under VIO_MASK_X_CLAMP and are taken modulo dW under
+              VIO_MASK_X_WRAP (the seam of a 360 degree frame).  r >= dW or r >= dH is legal, r = 0 a no-op.
+     warp     for an erp_warp (destination wW x wH, source sW x sH) and a source-space mask, sW x sH u8 or NULL (every
+              source pixel usable): a warp pixel is usable iff its map entry is valid and each of its four taps p00,
+              p01, p10, p11 is usable, whatever their weights; a tap column under X_WRAP is taken modulo sW and a tap
+              row under Y_REPLICATE is clamped, and the mask is read there; under a CONSTANT border a tap outside the
+              source is not usable.  With a NULL mask: no border_value and no invalid pixel enters the output.  A warp
+              larger than the plane asked for is then reduced as above, erosion comes last; a warp smaller on either
+              axis is VIO_ENOSYS, a warp of another context VIO_EINVAL.
+   A call is valid if every size is in [1, 65535], stride >= the source width, dst_stride >= dW, r in [0, 255] and
+   border_x known; otherwise VIO_EINVAL.  The output is 0 / 255.
+   Held by a tracker or front end, a mask has two effects: (1) the GFTT mask of erp_tracker_run and of the front
+   end's first-frame detection and re-detection is polar AND boundary AND usable AND NOT discs; (2) a tracked point
+   survives iff status AND NOT polar AND NOT boundary AND usable(xi, yi), xi = (int)rintf(x), yi = (int)rintf(y)
+   (round half to even, as the disc centres; a rounded position outside [0, W) x [0, H) is not usable), before
+   RANSAC: its sample stream is erp_ransac_samples(seed, n_good, iters) with the new n_good.  Without a mask nothing
+   changes and no extra kernel is launched.  Equalisation histograms still see masked pixels and LK still reads
+   them: erosion keeps LK windows off the mask's edge. */
+enum { VIO_MASK_X_CLAMP = 0, VIO_MASK_X_WRAP = 1 };
+typedef struct {
+    int32_t erode_radius;  /* r, tracker pixels */
+    int32_t border_x;      /* VIO_MASK_X_* */
+} erp_mask_params;
+/* host only: the argument check of erp_mask_build* without a context: VIO_OK, VIO_EINVAL or VIO_ENOSYS */
+int erp_mask_check(int sW, int sH, int stride, int dW, int dH, int dst_stride, const erp_mask_params* p);
+/* sW x sH mask -> dW x dH 0 / 255.  Blocking; host buffers. */
+int erp_mask_build(vio_ctx* ctx, const uint8_t* mask, int sW, int sH, int stride, int dW, int dH,
+                   const erp_mask_params* p, uint8_t* dst, int dst_stride);
+/* the same for DEVICE buffers, async on the context stream; no alignment is required of the pointers or the strides
+   and the padding of the destination rows is not written.  (The first call with a new pair of sizes uploads the
+   footprint tables after draining the stream; later calls with those sizes do not wait.) */
+int erp_mask_build_device(vio_ctx* ctx, const uint8_t* mask, int sW, int sH, int stride, int dW, int dH,
+                          const erp_mask_params* p, uint8_t* dst, int dst_stride);
+/* through a warp: src_mask is sW x sH of the warp's source (host) or NULL; dst is dW x dH, dW <= wW, dH <= wH.
+   Blocking. */
+int erp_mask_build_warped(erp_warp* w, const uint8_t* src_mask, int stride, int dW, int dH, const erp_mask_params* p,
+                          uint8_t* dst, int dst_stride);
+/* device time (ms) of the last build's launches on this context, a tracker's or front end's included (waits) */
+int erp_mask_kernel_ms(vio_ctx* ctx, double* ms);
+/* The tracker's mask: W x H is the tracker's size or larger (a camera-resolution mask is reduced).  mask == NULL
+   clears it: back to the maskless pipeline, bitwise.  A failed call leaves the previous mask in place.  Setting or
+   clearing applies to every later erp_tracker_run. */
+int erp_tracker_set_mask(erp_tracker* t, const uint8_t* mask, int W, int H, int stride, const erp_mask_params* p);
+/* the same from a DEVICE mask, async on the context stream and without a host synchronisation (per-frame masks of a
+   network on the same GPU); the mask must stay unchanged until the stream has passed the build */
+int erp_tracker_set_mask_device(erp_tracker* t, const uint8_t* dmask, int W, int H, int stride,
+                                const erp_mask_params* p);
+/* the usable region of `w`'s destination (src_mask: host, the warp's source size, or NULL), reduced to the tracker's
+   size when the warp is larger: the mask that goes with erp_tracker_upload_warped */
+int erp_tracker_set_mask_warped(erp_tracker* t, erp_warp* w, const uint8_t* src_mask, int stride,
+                                const erp_mask_params* p);
+/* the mask in use as 0 / 255 at the tracker's size (host, stride >= W); all 255 when none is set.  Blocking. */
+int erp_tracker_get_mask(erp_tracker* t, uint8_t* out, int stride);
+/* the front end's mask: applies to every later frame, whichever erp_frontend_track* brings it, and composes with
+   the equalisation; the arguments and rules are those of erp_tracker_set_mask* */
+int erp_frontend_set_mask(erp_frontend* f, const uint8_t* mask, int W, int H, int stride, const erp_mask_params* p);
+int erp_frontend_set_mask_device(erp_frontend* f, const uint8_t* dmask, int W, int H, int stride,
+                                 const erp_mask_params* p);
+int erp_frontend_set_mask_warped(erp_frontend* f, erp_warp* w, const uint8_t* src_mask, int stride,
+                                 const erp_mask_params* p);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

@@ -234,6 +234,13 @@ def lib():
     return L
 
 
+def _kernel_ms(ctx, handle, name):
+    """HIP-event time in ms of the last launch behind the C entry point `name` (a *_kernel_ms of `handle`)"""
+    ms = C.c_double()
+    ctx.check(getattr(lib(), name)(handle, C.byref(ms)), name)
+    return ms.value
+
+
 class Context:
     """vio_ctx wrapper: one HIP device + stream."""
 
@@ -331,9 +338,7 @@ class Context:
         return abi.mono_init_result_dict(R), M[:n], X[:n]
 
     def mono_init_kernel_ms(self):
-        ms = C.c_double()
-        self.check(lib().vio_mono_init_kernel_ms(self.h, C.byref(ms)), "vio_mono_init_kernel_ms")
-        return ms.value
+        return _kernel_ms(self, self.h, "vio_mono_init_kernel_ms")
 
     # ---- IMU preintegration ----
     def imu_preintegrate(self, samples, t_start, t_end, gyro_bias=None, accel_bias=None, noise=None):
@@ -353,9 +358,7 @@ class Context:
                    "vio_imu_preintegrate_device")
 
     def imu_kernel_ms(self):
-        ms = C.c_double()
-        self.check(lib().vio_imu_preintegrate_kernel_ms(self.h, C.byref(ms)), "vio_imu_preintegrate_kernel_ms")
-        return ms.value
+        return _kernel_ms(self, self.h, "vio_imu_preintegrate_kernel_ms")
 
     # ---- two-view triangulation ----
     def triangulate(self, T_cw, pairs, bearings, width):
@@ -381,9 +384,7 @@ class Context:
                                                 valid_ptr, err_ptr), "vio_triangulate_device")
 
     def triangulate_kernel_ms(self):
-        ms = C.c_double()
-        self.check(lib().vio_triangulate_kernel_ms(self.h, C.byref(ms)), "vio_triangulate_kernel_ms")
-        return ms.value
+        return _kernel_ms(self, self.h, "vio_triangulate_kernel_ms")
 
     # ---- frame preprocessing ----
     def resize_area(self, img, dW, dH):
@@ -485,9 +486,7 @@ class Context:
                                              dst_stride), "erp_equalize_device")
 
     def equalize_kernel_ms(self):
-        ms = C.c_double()
-        self.check(lib().erp_equalize_kernel_ms(self.h, C.byref(ms)), "erp_equalize_kernel_ms")
-        return ms.value
+        return _kernel_ms(self, self.h, "erp_equalize_kernel_ms")
 
     def set_equalize_stage_timing(self, on):
         """erp_equalize_set_stage_timing: later equalize launches record an event between their stages."""
@@ -513,14 +512,10 @@ class Context:
                                                dst_stride), "erp_mask_build_device")
 
     def mask_kernel_ms(self):
-        ms = C.c_double()
-        self.check(lib().erp_mask_kernel_ms(self.h, C.byref(ms)), "erp_mask_kernel_ms")
-        return ms.value
+        return _kernel_ms(self, self.h, "erp_mask_kernel_ms")
 
     def resize_kernel_ms(self):
-        ms = C.c_double()
-        self.check(lib().erp_resize_area_kernel_ms(self.h, C.byref(ms)), "erp_resize_area_kernel_ms")
-        return ms.value
+        return _kernel_ms(self, self.h, "erp_resize_area_kernel_ms")
 
     # ---- ERP feature tracking ----
     def klt_track(self, prev, curr, pts, params=None):
@@ -892,9 +887,7 @@ class Warp:
         self.ctx.check(lib().erp_warp_set_route(self.h, int(route)), "erp_warp_set_route")
 
     def kernel_ms(self):
-        ms = C.c_double()
-        self.ctx.check(lib().erp_warp_kernel_ms(self.h, C.byref(ms)), "erp_warp_kernel_ms")
-        return ms.value
+        return _kernel_ms(self.ctx, self.h, "erp_warp_kernel_ms")
 
     def close(self):
         if self.h:

@@ -791,17 +791,7 @@ void vio_ctx_destroy(vio_ctx* ctx) {
         if (p) (void)hipFree(p);
     for (void* p : ctx->hbufs)
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : ctx->imu_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->tri_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->rsz_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->init_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->eq_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->mask_ev)
+    for (hipEvent_t e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -8,6 +8,10 @@
 
 #include "vio360.h"
 
+// first event of each module's timing in vio_ctx::ev: start / end of its last launch (equalisation: start /
+// histograms done / LUTs done / end)
+enum { kEvImu = 0, kEvTri = 2, kEvResize = 4, kEvInit = 6, kEvEq = 8, kEvMask = 12, kEvCount = 14 };
+
 struct vio_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -18,32 +22,22 @@ struct vio_ctx {
     // grow-only pinned host staging buffers keyed by slot
     std::vector<void*> hbufs;
     std::vector<size_t> hcaps;
-    // IMU preintegration kernel timing (created on first use)
-    hipEvent_t imu_ev[2] = {nullptr, nullptr};
-    float imu_ms = -1.f;
-    // triangulation kernel timing (created on first use)
-    hipEvent_t tri_ev[2] = {nullptr, nullptr};
-    // INTER_AREA resize kernel timing (created on first use)
-    hipEvent_t rsz_ev[2] = {nullptr, nullptr};
+    // kernel timing of every module: the events of kEv* (created on first use, frame_io.h events_ready)
+    hipEvent_t ev[kEvCount] = {};
+    float imu_ms = -1.f;  // < 0: no IMU preintegration has run on this context
     // (W, dW, H, dH) of the general INTER_AREA tap tables now in kSlotResizeTabX / kSlotResizeTabY
     int rsz_tab_key[4] = {0, 0, 0, 0};
     int rsz_max_x_taps = 0;  // the largest tap count of a column of those tables
     // colour ingest execution route (erp_ingest_set_route)
     int ingest_route = VIO_INGEST_ROUTE_AUTO;
-    // monocular initialisation kernels timing (created on first use)
-    hipEvent_t init_ev[2] = {nullptr, nullptr};
     // window-BA execution route (vio_ctx_set_ba_route)
     int ba_route = VIO_BA_ROUTE_AUTO;
     // global-BA state kept between solves (ba_global_host.cpp GbaCache: look-ahead stream, captured graph)
     std::shared_ptr<void> gba_cache;
-    // equalisation: start / histograms done / LUTs done / end of the last erp_equalize_device (created on first use);
-    // the two inner events are recorded only under erp_equalize_set_stage_timing
-    hipEvent_t eq_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // equalisation: the two inner events of kEvEq are recorded only under erp_equalize_set_stage_timing
     bool eq_stage_timing = false;
     bool eq_staged = false;  // the last launch recorded the inner events
-    // region masks: start / end of the last build's launches (created on first use), and the (sW, dW, sH, dH) of the
-    // footprint tables now in kSlotMaskTab
-    hipEvent_t mask_ev[2] = {nullptr, nullptr};
+    // region masks: the (sW, dW, sH, dH) of the footprint tables now in kSlotMaskTab
     int mask_tab_key[4] = {0, 0, 0, 0};
 };
 
@@ -59,8 +53,7 @@ void* ctx_host_buffer(vio_ctx* ctx, int slot, size_t bytes);
 enum { kSlotImuData = 8, kSlotImuIntervals = 9, kSlotImuOut = 10 };
 // scratch slots owned by vio_triangulate
 enum { kSlotTriIn = 11, kSlotTriOut = 12 };
-// scratch slots owned by erp_resize_area
-enum { kSlotResizeSrc = 13, kSlotResizeDst = 14 };
+// (slots 13, 14 and 21 to 23: the frame resize and ingest, resize.h)
 // staging of vio_ba_batch_pack to host memory
 enum { kSlotRecords = 15 };
 // vio_imu_init_solve inputs, outputs and per-problem scratch
@@ -73,10 +66,6 @@ enum { kSlotLie = 18 };
 enum { kSlotBaSolve = 19 };
 // the global BA solves' arena (inputs, outputs, the dense reduced system and the rest of the state)
 enum { kSlotGbaSolve = 20 };
-// erp_resize_area_any: the per-output-column / per-output-row tap tables of the general path
-enum { kSlotResizeTabX = 21, kSlotResizeTabY = 22 };
-// erp_ingest_device, two-pass route: the grey camera-resolution plane between the convert and the resize
-enum { kSlotIngestPlane = 23 };
 // erp_equalize*: per-workgroup partial histograms, the tiles' LUTs, and the host entry point's frame
 enum { kSlotEqHist = 25, kSlotEqLut = 26, kSlotEqSrc = 27, kSlotEqDst = 28 };
 // (slots 29 to 33: the region-mask builds, mask.h)

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "equalize.h"
+#include "frame_io.h"
 
 using namespace vio360;
 
@@ -154,16 +155,17 @@ int erp_equalize_device(vio_ctx* ctx, const uint8_t* src, int W, int H, int stri
         set_error(ctx, "erp_equalize: device allocation failed");
         return VIO_ENOMEM;
     }
-    for (hipEvent_t& ev : ctx->eq_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
+    hipEvent_t* ev = ctx->ev + kEvEq;
+    int rc;
+    if ((rc = events_ready(ctx, ev, 4))) return rc;
     const bool staged = ctx->eq_stage_timing;
-    VIO_HIP(ctx, hipEventRecord(ctx->eq_ev[0], ctx->stream));
+    VIO_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     VIO_HIP(ctx, launch_eq_hist(a, ctx->stream));
-    if (staged) VIO_HIP(ctx, hipEventRecord(ctx->eq_ev[1], ctx->stream));
+    if (staged) VIO_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
     VIO_HIP(ctx, launch_eq_lut(a, ctx->stream));
-    if (staged) VIO_HIP(ctx, hipEventRecord(ctx->eq_ev[2], ctx->stream));
+    if (staged) VIO_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
     VIO_HIP(ctx, launch_eq_apply(a, ctx->stream));
-    VIO_HIP(ctx, hipEventRecord(ctx->eq_ev[3], ctx->stream));
+    VIO_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
     ctx->eq_staged = staged;
     return VIO_OK;
 }
@@ -175,30 +177,16 @@ int erp_equalize(vio_ctx* ctx, const uint8_t* src, int W, int H, int stride, con
         set_error(ctx, "erp_equalize: bad sizes, mode, tiles, clip limit or border mode");
         return VIO_EINVAL;
     }
-    const int sp = (W + 15) & ~15;
-    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotEqSrc, (size_t)sp * H));
-    uint8_t* d_dst = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotEqDst, (size_t)sp * H));
-    if (!d_src || !d_dst) {
-        set_error(ctx, "erp_equalize: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, src, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    int rc;
-    if ((rc = erp_equalize_device(ctx, d_src, W, H, sp, 1, p, d_dst, sp))) return rc;
-    VIO_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, d_dst, sp, W, H, hipMemcpyDeviceToHost, ctx->stream));
-    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VIO_OK;
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    int sp = 0, dp = 0, rc;
+    if ((rc = stage_rows(ctx, kSlotEqSrc, src, stride, W, H, 16, "erp_equalize", &d_src, &sp))) return rc;
+    if ((rc = scratch_rows(ctx, kSlotEqDst, W, H, 16, "erp_equalize", &d_dst, &dp))) return rc;
+    if ((rc = erp_equalize_device(ctx, d_src, W, H, sp, 1, p, d_dst, dp))) return rc;
+    return fetch_rows(ctx, d_dst, dp, dst, dst_stride, W, H);
 }
 
 int erp_equalize_kernel_ms(vio_ctx* ctx, double* ms) {
-    if (!ctx || !ms || !ctx->eq_ev[3]) return VIO_EINVAL;
-    float f = 0.f;
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipEventSynchronize(ctx->eq_ev[3]));
-    VIO_HIP(ctx, hipEventElapsedTime(&f, ctx->eq_ev[0], ctx->eq_ev[3]));
-    *ms = f;
-    return VIO_OK;
+    return ctx ? events_ms(ctx, ctx->ev[kEvEq], ctx->ev[kEvEq + 3], ms) : VIO_EINVAL;
 }
 
 int erp_equalize_set_stage_timing(vio_ctx* ctx, int on) {
@@ -208,15 +196,12 @@ int erp_equalize_set_stage_timing(vio_ctx* ctx, int on) {
 }
 
 int erp_equalize_stage_ms(vio_ctx* ctx, double* hist_ms, double* lut_ms, double* apply_ms) {
-    if (!ctx || !hist_ms || !lut_ms || !apply_ms || !ctx->eq_ev[3] || !ctx->eq_staged) return VIO_EINVAL;
-    float f[3] = {0.f, 0.f, 0.f};
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipEventSynchronize(ctx->eq_ev[3]));
-    for (int i = 0; i < 3; ++i) VIO_HIP(ctx, hipEventElapsedTime(&f[i], ctx->eq_ev[i], ctx->eq_ev[i + 1]));
-    *hist_ms = f[0];
-    *lut_ms = f[1];
-    *apply_ms = f[2];
-    return VIO_OK;
+    if (!ctx || !hist_ms || !lut_ms || !apply_ms || !ctx->eq_staged) return VIO_EINVAL;
+    const hipEvent_t* ev = ctx->ev + kEvEq;
+    double* out[3] = {hist_ms, lut_ms, apply_ms};
+    int rc = VIO_OK;
+    for (int i = 0; i < 3 && !rc; ++i) rc = events_ms(ctx, ev[i], ev[i + 1], out[i]);
+    return rc;
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "ctx.h"
+#include "frame_io.h"
 
 namespace vio360 {
 
@@ -293,13 +293,14 @@ using namespace vio360;
 
 static int launch_preint(vio_ctx* ctx, const ImuArgs& a) {
     VIO_DEVICE(ctx);
-    for (hipEvent_t& ev : ctx->imu_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
-    VIO_HIP(ctx, hipEventRecord(ctx->imu_ev[0], ctx->stream));
+    hipEvent_t* ev = ctx->ev + kEvImu;
+    int rc;
+    if ((rc = events_ready(ctx, ev, 2))) return rc;
+    VIO_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     hipLaunchKernelGGL(imu_preint_kernel, dim3((a.n + kIntervalsPerBlock - 1) / kIntervalsPerBlock), dim3(64), 0,
                        ctx->stream, a);
     VIO_HIP(ctx, hipGetLastError());
-    VIO_HIP(ctx, hipEventRecord(ctx->imu_ev[1], ctx->stream));
+    VIO_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
     ctx->imu_ms = 0.f;  // resolved by vio_imu_preintegrate_kernel_ms
     return VIO_OK;
 }
@@ -382,13 +383,9 @@ extern "C" int vio_imu_preintegrate(vio_ctx* ctx, const vio_imu_data* imu, int n
 
 extern "C" int vio_imu_preintegrate_kernel_ms(vio_ctx* ctx, double* ms) {
     if (!ctx || !ms) return VIO_EINVAL;
-    if (ctx->imu_ms < 0.f || !ctx->imu_ev[1]) {
+    if (ctx->imu_ms < 0.f || !ctx->ev[kEvImu + 1]) {
         set_error(ctx, "vio_imu_preintegrate_kernel_ms: no preintegration has run on this context");
         return VIO_EINVAL;
     }
-    float f = 0.f;
-    VIO_HIP(ctx, hipEventSynchronize(ctx->imu_ev[1]));
-    VIO_HIP(ctx, hipEventElapsedTime(&f, ctx->imu_ev[0], ctx->imu_ev[1]));
-    *ms = f;
-    return VIO_OK;
+    return events_ms(ctx, ctx->ev[kEvImu], ctx->ev[kEvImu + 1], ms);
 }

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "frame_io.h"
 #include "mask.h"
 
 using namespace vio360;
@@ -78,20 +79,6 @@ int footprint_tables(vio_ctx* ctx, int sW, int dW, int sH, int dH, const int32_t
     return VIO_OK;
 }
 
-// host mask -> the context's device copy (rows padded to 16 bytes)
-int upload_mask(vio_ctx* ctx, const uint8_t* mask, int W, int H, int stride, uint8_t** d, int* pitch) {
-    const int sp = (W + 15) & ~15;
-    uint8_t* p = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskSrc, (size_t)sp * H));
-    if (!p) {
-        set_error(ctx, "erp_mask: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_HIP(ctx, hipMemcpy2DAsync(p, sp, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    *d = p;
-    *pitch = sp;
-    return VIO_OK;
-}
-
 // the plane of mask_enqueue as a 0 / 255 image: to a device image, or through the context's to a host one
 int build_image(vio_ctx* ctx, const uint8_t* d_src, int sW, int sH, long long stride, erp_warp* w, int dW, int dH,
                 const erp_mask_params* p, uint8_t* dst, int dst_stride, bool dst_on_host) {
@@ -105,12 +92,8 @@ int build_image(vio_ctx* ctx, const uint8_t* d_src, int sW, int sH, long long st
     if ((rc = mask_enqueue(ctx, d_src, sW, sH, stride, w, dW, dH, p, plane))) return rc;
     uint8_t* d_img = dst_on_host ? reinterpret_cast<uint8_t*>(plane + (size_t)mask_words(dW) * dH) : dst;
     VIO_HIP(ctx, launch_mask_unpack(plane, dW, dH, d_img, dst_on_host ? dW : dst_stride, ctx->stream));
-    VIO_HIP(ctx, hipEventRecord(ctx->mask_ev[1], ctx->stream));
-    if (dst_on_host) {
-        VIO_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, d_img, dW, dW, dH, hipMemcpyDeviceToHost, ctx->stream));
-        VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return VIO_OK;
+    VIO_HIP(ctx, hipEventRecord(ctx->ev[kEvMask + 1], ctx->stream));
+    return dst_on_host ? fetch_rows(ctx, d_img, dW, dst, dst_stride, dW, dH) : VIO_OK;
 }
 
 }  // namespace
@@ -121,6 +104,10 @@ int mask_warp_check(const erp_warp* w, const uint8_t* src_mask, int stride, int 
     if (!w || !w->ctx || params_check(p) || dW <= 0 || dH <= 0 || (src_mask && stride < w->sW)) return VIO_EINVAL;
     if (dW > w->dW || dH > w->dH) return VIO_ENOSYS;  // a warp smaller than the plane asked for
     return VIO_OK;
+}
+
+int mask_stage(vio_ctx* ctx, const uint8_t* mask, int W, int H, int stride, const char* who, uint8_t** d, int* pitch) {
+    return stage_rows(ctx, kSlotMaskSrc, mask, stride, W, H, 16, who, d, pitch);
 }
 
 int mask_enqueue(vio_ctx* ctx, const uint8_t* d_src, int sW, int sH, long long stride, erp_warp* w, int dW, int dH,
@@ -151,10 +138,10 @@ int mask_enqueue(vio_ctx* ctx, const uint8_t* d_src, int sW, int sH, long long s
     }
     const int32_t *fx = nullptr, *fy = nullptr;
     if (reduce && (rc = footprint_tables(ctx, pW, dW, pH, dH, &fx, &fy))) return rc;
-    for (hipEvent_t& ev : ctx->mask_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
+    hipEvent_t* ev = ctx->ev + kEvMask;
+    if ((rc = events_ready(ctx, ev, 2))) return rc;
     hipStream_t st = ctx->stream;
-    VIO_HIP(ctx, hipEventRecord(ctx->mask_ev[0], st));
+    VIO_HIP(ctx, hipEventRecord(ev[0], st));
     int stage = 0;
     const uint32_t* cur = nullptr;
     auto next_out = [&]() { return stage + 1 == n_stages ? out : tmp[stage & 1]; };
@@ -190,7 +177,7 @@ int mask_enqueue(vio_ctx* ctx, const uint8_t* d_src, int sW, int sH, long long s
         VIO_HIP(ctx, launch_mask_erode_v(cur, o, dW, dH, r, st));
         ++stage;
     }
-    VIO_HIP(ctx, hipEventRecord(ctx->mask_ev[1], st));
+    VIO_HIP(ctx, hipEventRecord(ev[1], st));
     return VIO_OK;
 }
 
@@ -225,7 +212,7 @@ int erp_mask_build(vio_ctx* ctx, const uint8_t* mask, int sW, int sH, int stride
     VIO_DEVICE(ctx);
     uint8_t* d_src = nullptr;
     int sp = 0;
-    if ((rc = upload_mask(ctx, mask, sW, sH, stride, &d_src, &sp))) return rc;
+    if ((rc = mask_stage(ctx, mask, sW, sH, stride, "erp_mask", &d_src, &sp))) return rc;
     return build_image(ctx, d_src, sW, sH, sp, nullptr, dW, dH, p, dst, dst_stride, true);
 }
 
@@ -242,18 +229,12 @@ int erp_mask_build_warped(erp_warp* w, const uint8_t* src_mask, int stride, int 
     VIO_DEVICE(ctx);
     uint8_t* d_src = nullptr;
     int sp = 0;
-    if (src_mask && (rc = upload_mask(ctx, src_mask, w->sW, w->sH, stride, &d_src, &sp))) return rc;
+    if (src_mask && (rc = mask_stage(ctx, src_mask, w->sW, w->sH, stride, "erp_mask", &d_src, &sp))) return rc;
     return build_image(ctx, d_src, w->sW, w->sH, sp, w, dW, dH, p, dst, dst_stride, true);
 }
 
 int erp_mask_kernel_ms(vio_ctx* ctx, double* ms) {
-    if (!ctx || !ms || !ctx->mask_ev[1]) return VIO_EINVAL;
-    float f = 0.f;
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipEventSynchronize(ctx->mask_ev[1]));
-    VIO_HIP(ctx, hipEventElapsedTime(&f, ctx->mask_ev[0], ctx->mask_ev[1]));
-    *ms = f;
-    return VIO_OK;
+    return ctx ? events_ms(ctx, ctx->ev[kEvMask], ctx->ev[kEvMask + 1], ms) : VIO_EINVAL;
 }
 
 }  // extern "C"

@@ -29,7 +29,7 @@
 
 #include <cmath>
 
-#include "ctx.h"
+#include "frame_io.h"
 #include "mono_init_dev.h"
 
 namespace vio360 {
@@ -410,12 +410,12 @@ extern "C" int vio_mono_init_solve(vio_ctx* ctx, const float* bearings1, const f
     a.iters = iters;
     a.p = *params;
     hipStream_t st = ctx->stream;
-    for (hipEvent_t& ev : ctx->init_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
+    hipEvent_t* ev = ctx->ev + kEvInit;
+    if (int rc = events_ready(ctx, ev, 2)) return rc;
     VIO_HIP(ctx, hipMemcpyAsync(dB1, bearings1, bB, hipMemcpyHostToDevice, st));
     VIO_HIP(ctx, hipMemcpyAsync(dB2, bearings2, bB, hipMemcpyHostToDevice, st));
     if (iters) VIO_HIP(ctx, hipMemcpyAsync(dS, samples, bS, hipMemcpyHostToDevice, st));
-    VIO_HIP(ctx, hipEventRecord(ctx->init_ev[0], st));
+    VIO_HIP(ctx, hipEventRecord(ev[0], st));
     if (iters) {
         hipLaunchKernelGGL(mono_hyp_kernel, dim3((iters + kHypLanes - 1) / kHypLanes), dim3(kHypLanes), 0, st, a);
         VIO_HIP(ctx, hipGetLastError());
@@ -424,7 +424,7 @@ extern "C" int vio_mono_init_solve(vio_ctx* ctx, const float* bearings1, const f
     }
     hipLaunchKernelGGL(mono_finish_kernel, dim3(1), dim3(kFinThreads), 0, st, a);
     VIO_HIP(ctx, hipGetLastError());
-    VIO_HIP(ctx, hipEventRecord(ctx->init_ev[1], st));
+    VIO_HIP(ctx, hipEventRecord(ev[1], st));
     VIO_HIP(ctx, hipMemcpyAsync(res, a.res, bR, hipMemcpyDeviceToHost, st));
     if (inlier_mask) VIO_HIP(ctx, hipMemcpyAsync(inlier_mask, a.mask, bM, hipMemcpyDeviceToHost, st));
     if (points) VIO_HIP(ctx, hipMemcpyAsync(points, a.points, bP, hipMemcpyDeviceToHost, st));
@@ -433,10 +433,5 @@ extern "C" int vio_mono_init_solve(vio_ctx* ctx, const float* bearings1, const f
 }
 
 extern "C" int vio_mono_init_kernel_ms(vio_ctx* ctx, double* ms) {
-    if (!ctx || !ms || !ctx->init_ev[1]) return VIO_EINVAL;
-    float f = 0.f;
-    VIO_HIP(ctx, hipEventSynchronize(ctx->init_ev[1]));
-    VIO_HIP(ctx, hipEventElapsedTime(&f, ctx->init_ev[0], ctx->init_ev[1]));
-    *ms = f;
-    return VIO_OK;
+    return ctx ? events_ms(ctx, ctx->ev[kEvInit], ctx->ev[kEvInit + 1], ms) : VIO_EINVAL;
 }

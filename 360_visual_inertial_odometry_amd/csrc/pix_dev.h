@@ -37,6 +37,28 @@ inline PixSrc pix_source(int format, int luma) {
     return p;
 }
 
+// the rules of every entry point that takes a pixel format: a known format, for colour a known luma rule, an even
+// width W for 4:2:2; *why names the broken one
+inline int pix_check(int format, int luma, int W, const char** why) {
+    *why = erp_pixel_bytes(format) < 0 ? "unknown pixel format"
+           : pix_is_colour(format) && luma != VIO_LUMA_CVTCOLOR && luma != VIO_LUMA_IMREAD ? "unknown luma rule"
+           : pix_is_422(format) && W % 2 ? "a 4:2:2 frame has an even width"
+                                         : nullptr;
+    return *why ? VIO_EINVAL : VIO_OK;
+}
+
+// can a kernel take each 4-byte pixel of the rows at src as one aligned dword (kPixDword)?
+inline bool pix_dword_ok(const uint8_t* src, int stride) {
+    return (reinterpret_cast<uintptr_t>(src) & 3) == 0 && stride % 4 == 0;
+}
+
+// byte offsets -> bit shifts: what kPixDword and kPixRun3 (and the warp's pair route) read
+inline void pix_to_bit_shifts(PixSrc* p) {
+    p->o0 *= 8;
+    p->o1 *= 8;
+    p->o2 *= 8;
+}
+
 #if defined(__HIPCC__)
 
 template <int MODE>

@@ -16,8 +16,9 @@
 #include <atomic>
 #include <vector>
 
-#include "ctx.h"
+#include "frame_io.h"
 #include "mask.h"
+#include "resize.h"
 #include "tracker_types.h"
 #include "warp.h"
 
@@ -459,10 +460,54 @@ int enqueue_gftt(erp_tracker* t, const uint8_t* img, int pitch, const uint8_t* m
 
 int upload_frame(erp_tracker* t, int slot, const uint8_t* img, int stride) {
     if (!img || stride < t->W) { set_error(t->ctx, "bad frame"); return VIO_EINVAL; }
-    VIO_DEVICE(t->ctx);
-    VIO_HIP(t->ctx, hipMemcpy2DAsync(t->lvl[slot][0], t->lp[0], img, stride, t->W, t->H, hipMemcpyHostToDevice,
-                                     t->ctx->stream));
-    return VIO_OK;
+    return upload_rows(t->ctx, t->lvl[slot][0], t->lp[0], img, stride, t->W, t->H);
+}
+
+// A host frame on its way into a tracker slot: any pixel format and size no smaller than the tracker's, as it is
+// or through a warp (then the frame is the warp's sW x sH source, and W, H are not looked at).
+struct FrameSrc {
+    const uint8_t* img;
+    int format, luma, W, H, stride;
+    erp_warp* warp;
+};
+
+// Brings the frame into slot `slot` as the tracker's W x H grey image, all on the context stream:
+//   a grey frame of the tracker's size: the direct copy;
+//   any other frame: staged, then luma + INTER_AREA in one pass (the convert-only pass at the tracker's size);
+//   a warp of the tracker's size: staged, then remapped into the slot;
+//   a larger warp: staged, remapped at the warp's size, then cv::resize(..., INTER_AREA) into the slot.
+int tracker_ingest(erp_tracker* t, int slot, const FrameSrc& f, const char* who) {
+    if (!t || slot < 0 || slot > 1 || !f.img) return VIO_EINVAL;
+    vio_ctx* ctx = t->ctx;
+    erp_warp* w = f.warp;
+    const auto fail = [&](int rc, const char* why) {
+        set_error(ctx, std::string(who) + ": " + why);
+        return rc;
+    };
+    int rc;
+    if (w) {
+        if (w->ctx != ctx) return fail(VIO_EINVAL, "the warp belongs to another context");
+        if ((rc = erp_warp_check(w, f.format, f.luma, f.stride, w->dW))) return rc;
+        if (w->dW < t->W || w->dH < t->H)
+            return fail(VIO_ENOSYS, "the warp's destination is smaller than the tracker's frame");
+    }
+    const int W = w ? w->sW : f.W, H = w ? w->sH : f.H, bpp = erp_pixel_bytes(f.format);
+    const long long row = (long long)W * bpp;
+    if (bpp < 0 || W <= 0 || H <= 0 || f.stride < row || row > (1 << 30))
+        return fail(VIO_EINVAL, "unknown pixel format or bad sizes");
+    if (!w && f.format == VIO_PIX_GRAY8 && W == t->W && H == t->H) return upload_frame(t, slot, f.img, f.stride);
+    uint8_t* dst = t->lvl[slot][0];
+    const int dp = t->lp[0];
+    VIO_DEVICE(ctx);
+    // source rows padded to 16 bytes: the resize fast path, dword loads for 4-byte pixels
+    uint8_t *d_src = nullptr, *d_warp = nullptr;
+    int sp = 0, wp = 0;
+    if ((rc = stage_rows(ctx, kSlotResizeSrc, f.img, f.stride, row, H, 16, who, &d_src, &sp))) return rc;
+    if (!w) return erp_ingest_device(ctx, d_src, f.format, f.luma, W, H, sp, 1, dst, t->W, t->H, dp);
+    if (w->dW == t->W && w->dH == t->H) return erp_warp_apply_device(w, d_src, f.format, f.luma, sp, 1, dst, dp);
+    if ((rc = scratch_rows(ctx, kSlotWarpDst, w->dW, w->dH, 16, who, &d_warp, &wp))) return rc;
+    if ((rc = erp_warp_apply_device(w, d_src, f.format, f.luma, sp, 1, d_warp, wp))) return rc;
+    return erp_resize_area_any_device(ctx, d_warp, w->dW, w->dH, wp, 1, dst, t->W, t->H, dp);
 }
 
 int read_corners(erp_tracker* t, float* out_xy, int* n_out) {
@@ -566,81 +611,23 @@ void erp_tracker_destroy(erp_tracker* t) {
 }
 
 int erp_tracker_upload(erp_tracker* t, int slot, const uint8_t* img, int stride) {
-    if (!t || slot < 0 || slot > 1) return VIO_EINVAL;
-    return upload_frame(t, slot, img, stride);
+    if (!t) return VIO_EINVAL;
+    return tracker_ingest(t, slot, {img, VIO_PIX_GRAY8, 0, t->W, t->H, stride, nullptr}, "erp_tracker_upload");
 }
 
 int erp_tracker_upload_resized(erp_tracker* t, int slot, const uint8_t* img, int W, int H, int stride) {
-    if (!t || slot < 0 || slot > 1 || !img || W <= 0 || H <= 0 || stride < W) return VIO_EINVAL;
-    if (W == t->W && H == t->H) return upload_frame(t, slot, img, stride);
-    vio_ctx* ctx = t->ctx;
-    VIO_DEVICE(ctx);
-    const int sp = (W + 15) & ~15;  // 16-byte rows: the resize fast path
-    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * H));
-    if (!d_src) {
-        set_error(ctx, "erp_tracker_upload_resized: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-    return erp_resize_area_any_device(ctx, d_src, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
+    return tracker_ingest(t, slot, {img, VIO_PIX_GRAY8, 0, W, H, stride, nullptr}, "erp_tracker_upload_resized");
 }
 
 int erp_tracker_upload_pixels(erp_tracker* t, int slot, const uint8_t* img, int format, int luma, int W, int H,
                               int stride) {
-    if (!t || slot < 0 || slot > 1 || !img) return VIO_EINVAL;
-    if (format == VIO_PIX_GRAY8) return erp_tracker_upload_resized(t, slot, img, W, H, stride);
-    vio_ctx* ctx = t->ctx;
-    const int bpp = erp_pixel_bytes(format);
-    if (bpp < 0 || W <= 0 || H <= 0 || (long long)stride < (long long)W * bpp || (long long)W * bpp > (1 << 30)) {
-        set_error(ctx, "erp_tracker_upload_pixels: unknown pixel format or bad sizes");
-        return VIO_EINVAL;
-    }
-    VIO_DEVICE(ctx);
-    const int sp = (W * bpp + 15) & ~15;  // the packed frame, rows padded to 16 bytes (dword loads for 4-byte pixels)
-    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * H));
-    if (!d_src) {
-        set_error(ctx, "erp_tracker_upload_pixels: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, (size_t)W * bpp, H, hipMemcpyHostToDevice, ctx->stream));
-    // a frame already at the tracker's size takes the convert-only pass
-    return erp_ingest_device(ctx, d_src, format, luma, W, H, sp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
+    return tracker_ingest(t, slot, {img, format, luma, W, H, stride, nullptr}, "erp_tracker_upload_pixels");
 }
 
 int erp_tracker_upload_warped(erp_tracker* t, int slot, erp_warp* w, const uint8_t* img, int format, int luma,
                               int stride) {
-    if (!t || slot < 0 || slot > 1 || !w || !img) return VIO_EINVAL;
-    vio_ctx* ctx = t->ctx;
-    if (w->ctx != ctx) {
-        set_error(ctx, "erp_tracker_upload_warped: the warp belongs to another context");
-        return VIO_EINVAL;
-    }
-    int rc;
-    if ((rc = erp_warp_check(w, format, luma, stride, w->dW))) return rc;
-    if (w->dW < t->W || w->dH < t->H) {
-        set_error(ctx, "erp_tracker_upload_warped: the warp's destination is smaller than the tracker's frame");
-        return VIO_ENOSYS;
-    }
-    const long long row = (long long)w->sW * erp_pixel_bytes(format);
-    if (row > (1 << 30)) {
-        set_error(ctx, "erp_tracker_upload_warped: bad sizes");
-        return VIO_EINVAL;
-    }
-    VIO_DEVICE(ctx);
-    const int sp = (int)((row + 15) & ~15LL);  // the packed frame, rows padded to 16 bytes (dword loads for 4-byte pixels)
-    const bool direct = w->dW == t->W && w->dH == t->H;
-    const int wp = (w->dW + 15) & ~15;  // supersampled route: 16-byte rows, the resize fast path
-    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * w->sH));
-    uint8_t* d_warp = direct ? nullptr : static_cast<uint8_t*>(ctx_buffer(ctx, kSlotWarpDst, (size_t)wp * w->dH));
-    if (!d_src || (!direct && !d_warp)) {
-        set_error(ctx, "erp_tracker_upload_warped: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, img, stride, (size_t)row, w->sH, hipMemcpyHostToDevice, ctx->stream));
-    if (direct) return erp_warp_apply_device(w, d_src, format, luma, sp, 1, t->lvl[slot][0], t->lp[0]);
-    // remap at the warp's size, then cv::resize(..., INTER_AREA) into the slot
-    if ((rc = erp_warp_apply_device(w, d_src, format, luma, sp, 1, d_warp, wp))) return rc;
-    return erp_resize_area_any_device(ctx, d_warp, w->dW, w->dH, wp, 1, t->lvl[slot][0], t->W, t->H, t->lp[0]);
+    if (!w) return VIO_EINVAL;
+    return tracker_ingest(t, slot, {img, format, luma, 0, 0, stride, w}, "erp_tracker_upload_warped");
 }
 
 int erp_tracker_equalize(erp_tracker* t, int slot, const erp_equalize_params* p) {
@@ -930,8 +917,7 @@ int erp_gftt(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H
     if (!(rc = upload_frame(t, 1, img, stride))) {
         if (mask) {
             if (!(rc = dalloc(t, &dmask, (size_t)t->lp[0] * H))) {
-                hipError_t e = hipMemcpy2DAsync(dmask, t->lp[0], mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream);
-                if (e != hipSuccess) rc = hip_fail(ctx, e, "mask upload");
+                rc = upload_rows(ctx, dmask, t->lp[0], mask, stride, W, H);
             }
         }
         if (!rc) rc = enqueue_gftt(t, t->lvl[1][0], t->lp[0], dmask, t->lp[0], max_corners, quality, min_dist, false,
@@ -1226,34 +1212,30 @@ static int frontend_track_slot1(erp_frontend* f, int* n_features) {
     return VIO_OK;
 }
 
+static int frontend_track_src(erp_frontend* f, const FrameSrc& src, const char* who, int* n_features) {
+    if (!f) return VIO_EINVAL;
+    const int rc = tracker_ingest(f->t, 1, src, who);
+    return rc ? rc : frontend_track_slot1(f, n_features);
+}
+
 int erp_frontend_track(erp_frontend* f, const uint8_t* img, int stride, int* n_features) {
-    if (!f || !img) return VIO_EINVAL;
-    int rc;
-    if ((rc = upload_frame(f->t, 1, img, stride))) return rc;
-    return frontend_track_slot1(f, n_features);
+    if (!f) return VIO_EINVAL;
+    return frontend_track_src(f, {img, VIO_PIX_GRAY8, 0, f->W, f->H, stride, nullptr}, "erp_frontend_track", n_features);
 }
 
 int erp_frontend_track_resized(erp_frontend* f, const uint8_t* img, int W, int H, int stride, int* n_features) {
-    if (!f || !img) return VIO_EINVAL;
-    int rc;
-    if ((rc = erp_tracker_upload_resized(f->t, 1, img, W, H, stride))) return rc;
-    return frontend_track_slot1(f, n_features);
+    return frontend_track_src(f, {img, VIO_PIX_GRAY8, 0, W, H, stride, nullptr}, "erp_frontend_track_resized", n_features);
 }
 
 int erp_frontend_track_pixels(erp_frontend* f, const uint8_t* img, int format, int luma, int W, int H, int stride,
                               int* n_features) {
-    if (!f || !img) return VIO_EINVAL;
-    int rc;
-    if ((rc = erp_tracker_upload_pixels(f->t, 1, img, format, luma, W, H, stride))) return rc;
-    return frontend_track_slot1(f, n_features);
+    return frontend_track_src(f, {img, format, luma, W, H, stride, nullptr}, "erp_frontend_track_pixels", n_features);
 }
 
 int erp_frontend_track_warped(erp_frontend* f, erp_warp* w, const uint8_t* img, int format, int luma, int stride,
                               int* n_features) {
-    if (!f || !w || !img) return VIO_EINVAL;
-    int rc;
-    if ((rc = erp_tracker_upload_warped(f->t, 1, w, img, format, luma, stride))) return rc;
-    return frontend_track_slot1(f, n_features);
+    if (!w) return VIO_EINVAL;
+    return frontend_track_src(f, {img, format, luma, 0, 0, stride, w}, "erp_frontend_track_warped", n_features);
 }
 
 int erp_frontend_set_equalize(erp_frontend* f, const erp_equalize_params* p) {
@@ -1319,15 +1301,10 @@ int erp_tracker_set_mask(erp_tracker* t, const uint8_t* mask, int W, int H, int 
         set_error(t->ctx, "erp_tracker_set_mask: bad sizes, stride, radius or border mode, or a mask smaller than the frame");
         return rc;
     }
-    vio_ctx* ctx = t->ctx;
-    VIO_DEVICE(ctx);
-    const int sp = (W + 15) & ~15;
-    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskSrc, (size_t)sp * H));
-    if (!d_src) {
-        set_error(ctx, "erp_tracker_set_mask: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    VIO_DEVICE(t->ctx);
+    uint8_t* d_src = nullptr;
+    int sp = 0;
+    if (int e = mask_stage(t->ctx, mask, W, H, stride, "erp_tracker_set_mask", &d_src, &sp)) return e;
     return tracker_build_mask(t, d_src, W, H, sp, nullptr, p);
 }
 
@@ -1346,15 +1323,9 @@ int erp_tracker_set_mask_warped(erp_tracker* t, erp_warp* w, const uint8_t* src_
     }
     VIO_DEVICE(ctx);
     uint8_t* d_src = nullptr;
-    const int sp = (w->sW + 15) & ~15;
-    if (src_mask) {
-        d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskSrc, (size_t)sp * w->sH));
-        if (!d_src) {
-            set_error(ctx, "erp_tracker_set_mask_warped: device allocation failed");
-            return VIO_ENOMEM;
-        }
-        VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, src_mask, stride, w->sW, w->sH, hipMemcpyHostToDevice, ctx->stream));
-    }
+    int sp = 0;
+    if (src_mask)
+        if (int e = mask_stage(ctx, src_mask, w->sW, w->sH, stride, "erp_tracker_set_mask_warped", &d_src, &sp)) return e;
     return tracker_build_mask(t, d_src, w->sW, w->sH, sp, w, p);
 }
 
@@ -1366,15 +1337,11 @@ int erp_tracker_get_mask(erp_tracker* t, uint8_t* out, int stride) {
     }
     vio_ctx* ctx = t->ctx;
     VIO_DEVICE(ctx);
-    uint8_t* d_img = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotMaskDst, (size_t)t->W * t->H));
-    if (!d_img) {
-        set_error(ctx, "erp_tracker_get_mask: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_HIP(ctx, launch_mask_unpack(t->d_static, t->W, t->H, d_img, t->W, ctx->stream));
-    VIO_HIP(ctx, hipMemcpy2DAsync(out, stride, d_img, t->W, t->W, t->H, hipMemcpyDeviceToHost, ctx->stream));
-    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VIO_OK;
+    uint8_t* d_img = nullptr;
+    int ip = 0;
+    if (int e = scratch_rows(ctx, kSlotMaskDst, t->W, t->H, 1, "erp_tracker_get_mask", &d_img, &ip)) return e;
+    VIO_HIP(ctx, launch_mask_unpack(t->d_static, t->W, t->H, d_img, ip, ctx->stream));
+    return fetch_rows(ctx, d_img, ip, out, stride, t->W, t->H);
 }
 
 int erp_frontend_set_mask(erp_frontend* f, const uint8_t* mask, int W, int H, int stride, const erp_mask_params* p) {

@@ -22,7 +22,7 @@
 
 #include <cmath>
 
-#include "ctx.h"
+#include "frame_io.h"
 
 namespace vio360 {
 
@@ -151,12 +151,13 @@ extern "C" int vio_triangulate_device(vio_ctx* ctx, const float* T_cw, int n_pos
     if (n == 0) return VIO_OK;
     TriArgs a{T_cw, n_poses, pose_pair, bearings, n, (float)width, points, valid, pixel_err};
     VIO_DEVICE(ctx);
-    for (hipEvent_t& ev : ctx->tri_ev)
-        if (!ev) VIO_HIP(ctx, hipEventCreate(&ev));
-    VIO_HIP(ctx, hipEventRecord(ctx->tri_ev[0], ctx->stream));
+    hipEvent_t* ev = ctx->ev + kEvTri;
+    int rc;
+    if ((rc = events_ready(ctx, ev, 2))) return rc;
+    VIO_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     hipLaunchKernelGGL(triangulate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
     VIO_HIP(ctx, hipGetLastError());
-    VIO_HIP(ctx, hipEventRecord(ctx->tri_ev[1], ctx->stream));
+    VIO_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
     return VIO_OK;
 }
 
@@ -202,10 +203,5 @@ extern "C" int vio_triangulate(vio_ctx* ctx, const float* T_cw, int n_poses, con
 }
 
 extern "C" int vio_triangulate_kernel_ms(vio_ctx* ctx, double* ms) {
-    if (!ctx || !ms || !ctx->tri_ev[1]) return VIO_EINVAL;
-    float f = 0.f;
-    VIO_HIP(ctx, hipEventSynchronize(ctx->tri_ev[1]));
-    VIO_HIP(ctx, hipEventElapsedTime(&f, ctx->tri_ev[0], ctx->tri_ev[1]));
-    *ms = f;
-    return VIO_OK;
+    return ctx ? events_ms(ctx, ctx->ev[kEvTri], ctx->ev[kEvTri + 1], ms) : VIO_EINVAL;
 }

@@ -10,8 +10,11 @@
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <string>
 #include <vector>
 
+#include "frame_io.h"
+#include "resize.h"
 #include "warp.h"
 
 using namespace vio360;
@@ -48,35 +51,19 @@ int pixel_mode(int format, int luma, const uint8_t* src, int stride, bool pair, 
     *px = pix_source(format, luma);
     if (format == VIO_PIX_GRAY8) return kPixGray;
     int mode = pix_is_422(format) ? kPixByte : kPixBytes3;
-    if (px->bpp == 4 && (pair || ((reinterpret_cast<uintptr_t>(src) & 3) == 0 && stride % 4 == 0))) mode = kPixDword;
-    if (pair || mode == kPixDword) {
-        px->o0 *= 8;
-        px->o1 *= 8;
-        px->o2 *= 8;
-    }
+    if (px->bpp == 4 && (pair || pix_dword_ok(src, stride))) mode = kPixDword;
+    if (pair || mode == kPixDword) pix_to_bit_shifts(px);
     return mode;
 }
 
 int warp_check(const erp_warp* w, int format, int luma, int stride, int dst_stride, int n_frames) {
     vio_ctx* ctx = w->ctx;
-    const int bpp = erp_pixel_bytes(format);
-    if (bpp < 0) {
-        if (ctx) set_error(ctx, "erp_warp: unknown pixel format");
-        return VIO_EINVAL;
-    }
-    if (pix_is_colour(format) && luma != VIO_LUMA_CVTCOLOR && luma != VIO_LUMA_IMREAD) {
-        if (ctx) set_error(ctx, "erp_warp: unknown luma rule");
-        return VIO_EINVAL;
-    }
-    if (pix_is_422(format) && w->sW % 2) {
-        if (ctx) set_error(ctx, "erp_warp: a 4:2:2 frame has an even width");
-        return VIO_EINVAL;
-    }
-    if ((long long)stride < (long long)w->sW * bpp || dst_stride < w->dW || n_frames < 0) {
-        if (ctx) set_error(ctx, "erp_warp: bad sizes");
-        return VIO_EINVAL;
-    }
-    return VIO_OK;
+    const char* why;
+    if (!pix_check(format, luma, w->sW, &why) &&
+        ((long long)stride < (long long)w->sW * erp_pixel_bytes(format) || dst_stride < w->dW || n_frames < 0))
+        why = "bad sizes";
+    if (why) set_error(ctx, std::string("erp_warp: ") + why);
+    return why ? VIO_EINVAL : VIO_OK;
 }
 
 struct Vec3 {
@@ -220,36 +207,19 @@ int erp_warp_apply(erp_warp* w, const uint8_t* src, int format, int luma, int st
     vio_ctx* ctx = w->ctx;
     int rc = warp_check(w, format, luma, stride, dst_stride, 1);
     if (rc) return rc;
-    const long long row = (long long)w->sW * erp_pixel_bytes(format);
-    const long long sp = (row + 15) & ~15LL;  // rows padded to 16 bytes (dword loads for 4-byte pixels)
-    const int dp = (w->dW + 3) & ~3;
-    if (sp > INT32_MAX) {
-        set_error(ctx, "erp_warp: bad sizes");
-        return VIO_EINVAL;
-    }
-    uint8_t* d_src = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeSrc, (size_t)sp * w->sH));
-    uint8_t* d_dst = static_cast<uint8_t*>(ctx_buffer(ctx, kSlotResizeDst, (size_t)dp * w->dH));
-    if (!d_src || !d_dst) {
-        set_error(ctx, "erp_warp: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipMemcpy2DAsync(d_src, sp, src, stride, row, w->sH, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = erp_warp_apply_device(w, d_src, format, luma, (int)sp, 1, d_dst, dp))) return rc;
-    VIO_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, d_dst, dp, w->dW, w->dH, hipMemcpyDeviceToHost, ctx->stream));
-    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VIO_OK;
+    // source rows padded to 16 bytes (dword loads for 4-byte pixels)
+    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    int sp = 0, dp = 0;
+    if ((rc = stage_rows(ctx, kSlotResizeSrc, src, stride, (long long)w->sW * erp_pixel_bytes(format), w->sH, 16,
+                         "erp_warp", &d_src, &sp)))
+        return rc;
+    if ((rc = scratch_rows(ctx, kSlotResizeDst, w->dW, w->dH, 4, "erp_warp", &d_dst, &dp))) return rc;
+    if ((rc = erp_warp_apply_device(w, d_src, format, luma, sp, 1, d_dst, dp))) return rc;
+    return fetch_rows(ctx, d_dst, dp, dst, dst_stride, w->dW, w->dH);
 }
 
 int erp_warp_kernel_ms(erp_warp* w, double* ms) {
-    if (!w || !w->ctx || !ms) return VIO_EINVAL;
-    vio_ctx* ctx = w->ctx;
-    float f = 0.f;
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipEventSynchronize(w->ev[1]));
-    VIO_HIP(ctx, hipEventElapsedTime(&f, w->ev[0], w->ev[1]));
-    *ms = f;
-    return VIO_OK;
+    return w && w->ctx ? events_ms(w->ctx, w->ev[0], w->ev[1], ms) : VIO_EINVAL;
 }
 
 // ---- map generators ----

@@ -520,7 +520,8 @@ class Context:
     # ---- ERP feature tracking ----
     def klt_track(self, prev, curr, pts, params=None):
         """cv::calcOpticalFlowPyrLK as FeatureTracker::TrackOpticalFlow calls it -> (next, status, err)."""
-        prev, curr = _u8img(prev), _u8img(curr)
+        prev = _u8rows(prev)
+        curr = _u8rows(curr, prev.strides[0])
         H, W = prev.shape
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
         n = len(pts)
@@ -528,20 +529,20 @@ class Context:
         st = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32)
         prm = params or default_klt_params()
-        self.check(lib().erp_klt_track(self.h, _p(prev), _p(curr), W, H, W, _p(pts), n, _p(nxt), _p(st), _p(err),
-                                       C.byref(prm)), "erp_klt_track")
+        self.check(lib().erp_klt_track(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), n, _p(nxt), _p(st),
+                                       _p(err), C.byref(prm)), "erp_klt_track")
         return nxt, st, err
 
     def gftt(self, img, mask=None, max_corners=1000, quality=0.01, min_dist=30.0):
         """cv::goodFeaturesToTrack(blockSize 3, useHarris false) -> (k, 2) float32 corners."""
-        img = _u8img(img)
+        img = _u8rows(img)
         H, W = img.shape
-        m = None if mask is None else _u8img(mask)
+        m = None if mask is None else _u8rows(mask, img.strides[0])
         cap = max_corners if max_corners > 0 else W * H
         out = np.zeros((cap, 2), np.float32)
         n = C.c_int()
-        self.check(lib().erp_gftt(self.h, _p(img), _p(m) if m is not None else None, W, H, W, int(max_corners),
-                                  float(quality), float(min_dist), _p(out), C.byref(n)), "erp_gftt")
+        self.check(lib().erp_gftt(self.h, _p(img), _p(m) if m is not None else None, W, H, img.strides[0],
+                                  int(max_corners), float(quality), float(min_dist), _p(out), C.byref(n)), "erp_gftt")
         return out[: n.value].copy()
 
     def rot_ransac(self, p0, p1, W, H, samples, thresh_rad=None):
@@ -626,6 +627,27 @@ def unpack_record(rec):
 
 def _u8img(a):
     return np.ascontiguousarray(a, np.uint8)
+
+
+def _u8rows(a, pitch=None):
+    """an (H, W) u8 frame with contiguous rows, left in place when its row stride is at least W (a view such as
+    buf[:, :W] of a wider buffer is passed as it is); with `pitch`, the rows are copied into a buffer of that
+    pitch when the frame's own row stride differs (a C-ABI call that takes one stride for two arrays)"""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        a = a.astype(np.uint8)
+    if a.ndim != 2:
+        raise VioError(f"a frame is an (H, W) array, got shape {a.shape}")
+    H, W = a.shape
+    if a.strides[1] != 1 or a.strides[0] < W:
+        a = np.ascontiguousarray(a)
+    if pitch is not None and a.strides[0] != pitch:
+        if pitch < W:
+            raise VioError(f"two frames of one call differ in width: a row of {W} bytes against a pitch of {pitch}")
+        buf = np.zeros((H, pitch), np.uint8)
+        buf[:, :W] = a
+        a = buf[:, :W]
+    return a
 
 
 def _p(a):
@@ -914,8 +936,8 @@ class Tracker:
         self.n = 0
 
     def upload(self, slot, img):
-        img = _u8img(img)
-        self.ctx.check(lib().erp_tracker_upload(self.h, slot, _p(img), img.shape[1]), "erp_tracker_upload")
+        img = _u8rows(img)
+        self.ctx.check(lib().erp_tracker_upload(self.h, slot, _p(img), img.strides[0]), "erp_tracker_upload")
 
     def upload_resized(self, slot, img):
         """erp_tracker_upload_resized: a camera-resolution frame, INTER_AREA-resized on the device."""

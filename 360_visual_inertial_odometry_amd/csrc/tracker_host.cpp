@@ -582,8 +582,10 @@ int erp_ransac_samples(uint32_t seed, int n, int iters, int32_t* out) {
     return VIO_OK;
 }
 
-int erp_tracker_create(vio_ctx* ctx, int W, int H, int max_points, int max_corners, erp_tracker** out) {
-    if (!ctx || !out || W < 8 || H < 8 || W > 65535 || H > 65535 || max_points < 0 || max_corners < 0)
+// min_side: erp_tracker_create's 8; 3 for the scratch tracker of erp_gftt, which admits W, H >= 3 (its kernels read
+// level 0 only, through reflect101: 3x3 neighbourhoods need no more)
+static int tracker_new(vio_ctx* ctx, int W, int H, int max_points, int max_corners, int min_side, erp_tracker** out) {
+    if (!ctx || !out || W < min_side || H < min_side || W > 65535 || H > 65535 || max_points < 0 || max_corners < 0)
         return VIO_EINVAL;
     *out = nullptr;
     DeviceScope _vio_dev_scope(ctx->device);
@@ -593,6 +595,10 @@ int erp_tracker_create(vio_ctx* ctx, int W, int H, int max_points, int max_corne
     if (rc) { tracker_free(t); delete t; return rc; }
     *out = t;
     return VIO_OK;
+}
+
+int erp_tracker_create(vio_ctx* ctx, int W, int H, int max_points, int max_corners, erp_tracker** out) {
+    return tracker_new(ctx, W, H, max_points, max_corners, 8, out);
 }
 
 int erp_tracker_gftt_fallbacks(erp_tracker* t, int* exact_tail, int* full_sort) {
@@ -911,7 +917,7 @@ int erp_gftt(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H
     if (max_corners == 0) max_corners = W * H;  // "no limit"
     VIO_DEVICE(ctx);
     erp_tracker* t = nullptr;
-    int rc = erp_tracker_create(ctx, W, H, 1, max_corners, &t);
+    int rc = tracker_new(ctx, W, H, 1, max_corners, 3, &t);  // down to the W, H >= 3 checked above
     if (rc) return rc;
     uint8_t* dmask = nullptr;
     if (!(rc = upload_frame(t, 1, img, stride))) {

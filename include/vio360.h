@@ -394,7 +394,8 @@ int erp_klt_track(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W,
                   const erp_klt_params* params);
 
 /* goodFeaturesToTrack(img, max_corners, quality, min_dist, mask, blockSize 3, useHarris false).
-   mask may be NULL.  out_xy holds up to max_corners float2, *n_out the count. */
+   mask may be NULL and shares the image's row stride.  W, H >= 3.  out_xy holds up to max_corners float2
+   (W * H for max_corners 0: no limit), *n_out the count. */
 int erp_gftt(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H, int stride,
              int max_corners, double quality, double min_dist, float* out_xy, int* n_out);
 

@@ -11,7 +11,8 @@ import weakref
 import numpy as np
 
 from . import abi
-from .abi import (VIO_BA_FULL, VIO_BA_LOCAL, VIO_BA_VI, VIO_PNP, BaOutput, BaProblem,  # noqa: F401
+from .abi import (VIO_BA_FULL, VIO_BA_LOCAL, VIO_BA_VI, VIO_PNP, VIO_SEAM_CUT, VIO_SEAM_WRAP, BaOutput,  # noqa: F401
+                  BaProblem,
                   ErpFrontendParams, ErpKltParams, ErpTrackerParams, default_frontend_params,
                   default_klt_params, default_tracker_params)
 
@@ -61,6 +62,7 @@ EXPORTS = [
     "erp_mask_check", "erp_mask_build", "erp_mask_build_device", "erp_mask_build_warped", "erp_mask_kernel_ms",
     "erp_tracker_set_mask", "erp_tracker_set_mask_device", "erp_tracker_set_mask_warped", "erp_tracker_get_mask",
     "erp_frontend_set_mask", "erp_frontend_set_mask_device", "erp_frontend_set_mask_warped",
+    "erp_seam_check", "erp_klt_track_seam", "erp_gftt_seam", "erp_tracker_set_seam", "erp_frontend_set_seam",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -194,6 +196,12 @@ def lib():
         L.erp_tracker_set_mask_warped.argtypes = [vp, vp, vp, C.c_int, mkp]
         L.erp_frontend_set_mask_warped.argtypes = [vp, vp, vp, C.c_int, mkp]
         L.erp_tracker_get_mask.argtypes = [vp, vp, C.c_int]
+    if hasattr(L, "erp_seam_check") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        L.erp_seam_check.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
+        L.erp_klt_track_seam.argtypes = L.erp_klt_track.argtypes + [C.c_int]
+        L.erp_gftt_seam.argtypes = L.erp_gftt.argtypes + [C.c_int]
+        L.erp_tracker_set_seam.argtypes = [vp, C.c_int]
+        L.erp_frontend_set_seam.argtypes = [vp, C.c_int]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -518,8 +526,9 @@ class Context:
         return _kernel_ms(self, self.h, "erp_resize_area_kernel_ms")
 
     # ---- ERP feature tracking ----
-    def klt_track(self, prev, curr, pts, params=None):
-        """cv::calcOpticalFlowPyrLK as FeatureTracker::TrackOpticalFlow calls it -> (next, status, err)."""
+    def klt_track(self, prev, curr, pts, params=None, seam=None):
+        """cv::calcOpticalFlowPyrLK as FeatureTracker::TrackOpticalFlow calls it -> (next, status, err).
+        seam (VIO_SEAM_*): erp_klt_track_seam; VIO_SEAM_WRAP tracks across the ERP seam, next.x in [0, W)."""
         prev = _u8rows(prev)
         curr = _u8rows(curr, prev.strides[0])
         H, W = prev.shape
@@ -529,20 +538,29 @@ class Context:
         st = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32)
         prm = params or default_klt_params()
-        self.check(lib().erp_klt_track(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), n, _p(nxt), _p(st),
-                                       _p(err), C.byref(prm)), "erp_klt_track")
+        if seam is None:
+            self.check(lib().erp_klt_track(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), n, _p(nxt),
+                                           _p(st), _p(err), C.byref(prm)), "erp_klt_track")
+        else:
+            self.check(lib().erp_klt_track_seam(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), n, _p(nxt),
+                                                _p(st), _p(err), C.byref(prm), int(seam)), "erp_klt_track_seam")
         return nxt, st, err
 
-    def gftt(self, img, mask=None, max_corners=1000, quality=0.01, min_dist=30.0):
-        """cv::goodFeaturesToTrack(blockSize 3, useHarris false) -> (k, 2) float32 corners."""
+    def gftt(self, img, mask=None, max_corners=1000, quality=0.01, min_dist=30.0, seam=None):
+        """cv::goodFeaturesToTrack(blockSize 3, useHarris false) -> (k, 2) float32 corners.
+        seam (VIO_SEAM_*): erp_gftt_seam; VIO_SEAM_WRAP detects on the cylinder (wrapped neighbours and distance)."""
         img = _u8rows(img)
         H, W = img.shape
         m = None if mask is None else _u8rows(mask, img.strides[0])
         cap = max_corners if max_corners > 0 else W * H
         out = np.zeros((cap, 2), np.float32)
         n = C.c_int()
-        self.check(lib().erp_gftt(self.h, _p(img), _p(m) if m is not None else None, W, H, img.strides[0],
-                                  int(max_corners), float(quality), float(min_dist), _p(out), C.byref(n)), "erp_gftt")
+        args = (self.h, _p(img), _p(m) if m is not None else None, W, H, img.strides[0], int(max_corners),
+                float(quality), float(min_dist), _p(out), C.byref(n))
+        if seam is None:
+            self.check(lib().erp_gftt(*args), "erp_gftt")
+        else:
+            self.check(lib().erp_gftt_seam(*args, int(seam)), "erp_gftt_seam")
         return out[: n.value].copy()
 
     def rot_ransac(self, p0, p1, W, H, samples, thresh_rad=None):
@@ -682,6 +700,11 @@ def warp_quantize(s, S, border_mode):
 def equalize_params(mode=VIO_EQ_CLAHE, tiles_x=8, tiles_y=8, clip_limit=3.0, border_x=VIO_EQ_X_CLAMP):
     """erp_equalize_params; the defaults are cv::createCLAHE(3.0, Size(8, 8)) as VINS-style trackers run it."""
     return abi.ErpEqualizeParams(int(mode), int(tiles_x), int(tiles_y), int(border_x), float(clip_limit))
+
+
+def seam_check(W, H, win=21, max_level=3, min_dist=30.0):
+    """erp_seam_check (host): VIO_OK when (W, H, win, max_level, min_dist) admit VIO_SEAM_WRAP, else VIO_EINVAL."""
+    return lib().erp_seam_check(int(W), int(H), int(win), int(max_level), float(min_dist))
 
 
 def mask_params(erode_radius=0, border_x=VIO_MASK_X_CLAMP):
@@ -978,6 +1001,10 @@ class Tracker:
         warp's source coordinates, or None), the mask that goes with upload_warped."""
         _set_mask_warped(self, "erp_tracker_set_mask_warped", warp, src_mask, params)
 
+    def set_seam(self, seam):
+        """erp_tracker_set_seam: VIO_SEAM_CUT (default) or VIO_SEAM_WRAP, from the next run on."""
+        self.ctx.check(lib().erp_tracker_set_seam(self.h, int(seam)), "erp_tracker_set_seam")
+
     def get_mask(self):
         """erp_tracker_get_mask: the mask in use as (H, W) u8 of 0 / 255; all 255 when none is set."""
         out = np.zeros((self.H, self.W), np.uint8)
@@ -1068,6 +1095,11 @@ class Frontend:
     def set_mask_warped(self, warp, src_mask=None, params=None):
         """erp_frontend_set_mask_warped: the usable region of `warp`'s destination, for track_warped."""
         _set_mask_warped(self, "erp_frontend_set_mask_warped", warp, src_mask, params)
+
+    def set_seam(self, seam):
+        """erp_frontend_set_seam: VIO_SEAM_CUT (default) or VIO_SEAM_WRAP (features are tracked and detected across
+        the ERP seam), from the next frame on."""
+        self.ctx.check(lib().erp_frontend_set_seam(self.h, int(seam)), "erp_frontend_set_seam")
 
     def track(self, img):
         img = _u8img(img)

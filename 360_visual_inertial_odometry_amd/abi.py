@@ -9,6 +9,8 @@ import numpy as np
 
 VIO_BA_LOCAL, VIO_BA_FULL, VIO_BA_VI, VIO_PNP = 0, 1, 2, 3
 VIO_TERM_CONVERGENCE, VIO_TERM_NO_CONVERGENCE, VIO_TERM_FAILURE = 0, 1, 2
+# seam mode of the ERP tracking path: the flat picture (default) or the frame continued periodically in x
+VIO_SEAM_CUT, VIO_SEAM_WRAP = 0, 1
 
 _u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int32)

@@ -51,9 +51,10 @@ hipError_t launch_mask_erode_h(const uint32_t* in, uint32_t* out, int W, int H, 
 hipError_t launch_mask_erode_v(const uint32_t* in, uint32_t* out, int W, int H, int r, hipStream_t st);
 // plane -> 0 / 255 bytes (any alignment of dst and its stride)
 hipError_t launch_mask_unpack(const uint32_t* bits, int W, int H, uint8_t* dst, long long dstride, hipStream_t st);
-// usable[i] = 1 iff (rintf(x_i), rintf(y_i)) is inside the frame and not excluded
+// usable[i] = 1 iff (rintf(x_i), rintf(y_i)) is inside the frame and not excluded (x_wrap, the tracker's seam wrap
+// mode: a column that rounds to W is column 0)
 hipError_t launch_mask_gather(const float* pts, int n, const uint32_t* bits, int W, int H, uint8_t* usable,
-                              hipStream_t st);
+                              hipStream_t st, int x_wrap = 0);
 
 // Enqueues on the context stream the build of the dW x dH exclusion plane `out` (device, mask_words(dW) * dH
 // words) from a DEVICE source: without a warp an sW x sH u8 mask, with one the warp's source-space mask (or null).

@@ -174,10 +174,12 @@ __global__ void __launch_bounds__(256) mask_unpack_kernel(const uint32_t* bits, 
 }
 
 __global__ void __launch_bounds__(256) mask_gather_kernel(const float* pts, int n, const uint32_t* bits, int W, int H,
-                                                          int words, uint8_t* usable) {
+                                                          int words, uint8_t* usable, int x_wrap) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int xi = (int)rintf(pts[2 * i]), yi = (int)rintf(pts[2 * i + 1]);
+    int xi = (int)rintf(pts[2 * i]);
+    const int yi = (int)rintf(pts[2 * i + 1]);
+    if (x_wrap && xi == W) xi = 0;  // seam wrap mode: a column within half a pixel of the seam rounds across it
     bool u = (unsigned)xi < (unsigned)W && (unsigned)yi < (unsigned)H;
     if (u) u = !((bits[(size_t)yi * words + (xi >> 5)] >> (xi & 31)) & 1u);
     usable[i] = u ? 1 : 0;
@@ -217,10 +219,10 @@ hipError_t launch_mask_unpack(const uint32_t* bits, int W, int H, uint8_t* dst, 
 }
 
 hipError_t launch_mask_gather(const float* pts, int n, const uint32_t* bits, int W, int H, uint8_t* usable,
-                              hipStream_t st) {
+                              hipStream_t st, int x_wrap) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(mask_gather_kernel, dim3((n + 255) >> 8), dim3(256), 0, st, pts, n, bits, W, H, mask_words(W),
-                       usable);
+                       usable, x_wrap);
     return hipGetLastError();
 }
 

@@ -17,6 +17,10 @@
 //                        (response, address) keys; a top-K histogram cut, a sort and one
 //                        workgroup's greedy min-distance pass finish.  (Recomputing the map in
 //                        pass 2 cost more than its 2 x 4 B/px round trip through HBM / MALL.)
+// Seam wrap mode (VIO_SEAM_WRAP, the x_wrap flag of the argument blocks): every stage on the horizontally periodic
+// continuation of the frame -- wrapped border columns, no sideways exit and no side margins, discs and the
+// min-distance test on the cylinder, detection through the map path.  Off by default; on the pipeline's critical
+// path the flag selects a template instance, so the default kernels are the code they were.
 // Float expressions follow tracker_oracle.c literally and the file is built with
 // -ffp-contract=off, so results are bitwise those of the oracle.
 #include <float.h>
@@ -54,6 +58,15 @@ __device__ __forceinline__ int reflect101(int p, int n) {
     return p;
 }
 
+// Seam wrap mode: column p of the frame continued periodically, for p in [-n, 2n) -- one conditional add or
+// subtract, no division.  Columns further right are never part of a result (they lie beyond the last output
+// of a partial tile); the min only keeps their address inside the row.
+__device__ __forceinline__ int wrap_x(int p, int n) {
+    return p < 0 ? p + n : (p >= n ? min(p - n, n - 1) : p);
+}
+// the column border of an edge path: REFLECT_101, or the periodic continuation in wrap mode (wave-uniform flag)
+__device__ __forceinline__ int border_x(int p, int n, int x_wrap) { return x_wrap ? wrap_x(p, n) : reflect101(p, n); }
+
 // MASKED: G.static_bits (a region mask's exclusion plane) is part of the static region (pass 1 with a mask set; the
 // maskless instance is the code it was before masks existed)
 template <bool MASKED = false>
@@ -75,7 +88,9 @@ __device__ __forceinline__ bool lm_disc(const GfArgs& G, int x, int y) {
 // profiles/r6c_ab_pyr.log).
 constexpr int PD_BX = 64;
 constexpr int PD_TW = 160;
-template <int BY>
+// WRAP (seam wrap mode, src.x_wrap): the edge columns are patched from the opposite side of the level instead of
+// reflected; the default instance is the code as it was
+template <int BY, bool WRAP = false>
 __global__ void __launch_bounds__(256) pyr_down_kernel(PyrLevelPair src, PyrLevelPair dst) {
     constexpr int PD_BY = BY, PD_TH = 2 * PD_BY + 4;
     __shared__ uint8_t tile[PD_TH][PD_TW];
@@ -111,7 +126,8 @@ __global__ void __launch_bounds__(256) pyr_down_kernel(PyrLevelPair src, PyrLeve
         __syncthreads();
         for (int e = threadIdx.x; e < PD_TH * (2 * PD_BX + 4); e += 256) {
             const int ty = e / (2 * PD_BX + 4), x = 2 * ox - 2 + e % (2 * PD_BX + 4);
-            if (x < 0 || x >= sw) tile[ty][x - cx0] = s[(size_t)reflect101(sy0 + ty, sh) * sp + reflect101(x, sw)];
+            if (x < 0 || x >= sw)
+                tile[ty][x - cx0] = s[(size_t)reflect101(sy0 + ty, sh) * sp + (WRAP ? wrap_x(x, sw) : reflect101(x, sw))];
         }
     }
     __syncthreads();
@@ -148,13 +164,8 @@ __global__ void __launch_bounds__(256) pyr_down_kernel(PyrLevelPair src, PyrLeve
 // LK.  One workgroup per point.
 constexpr int LK_WAVES = 4;  // one point per workgroup of LK_WAVES waves
 constexpr int LK_THREADS = 64 * LK_WAVES;
-constexpr int LK_WIN_MAX = 21;
 constexpr int LK_NIT = (LK_WIN_MAX * LK_WIN_MAX + LK_THREADS - 1) / LK_THREADS;  // patch pixels per lane
-constexpr int LK_T = LK_WIN_MAX + 3;  // prev tile (patch + 1 bilinear + 1 Scharr each side)
-constexpr int LK_D = LK_WIN_MAX + 1;  // derivative / next tile
-
-constexpr int LK_MARGIN = 8;                 // staged next-frame region: the window +- 8 px
-constexpr int LK_R = LK_D + 2 * LK_MARGIN;
+// (LK_T, LK_D, LK_MARGIN, LK_R: the staging tiles' sizes, tracker_types.h)
 
 struct LkShared {
     uint8_t Jr[LK_R * LK_R];                 // next-frame region (reflect-101 values), origin (rx0, ry0)
@@ -206,9 +217,20 @@ __device__ __forceinline__ long long wg_sum_i64(long long v, double* red) {
     return (long long)t;
 }
 
+// Seam wrap mode: the column of the frame under the unwrapped column x0 of a staged tile's origin.  The iteration
+// may carry x0 any distance from the frame, so this is a true remainder -- once per staged tile, workgroup-uniform,
+// never per pixel.
+__device__ __forceinline__ int lk_fold_origin(int x0, int w) {
+    const int m = x0 % w;
+    return m < 0 ? m + w : m;
+}
+
 // make the staged region cover the (win+1)^2 window at (ix, iy); restage around it when it does
 // not (one global round trip per level instead of one per iteration).  Values are the
 // REFLECT_101-padded pixels, exactly what a per-window load would read.  Workgroup-uniform.
+// WRAP (seam wrap mode): rx0 stays in the iteration's unwrapped coordinates; the columns are those of the
+// periodic continuation (lk_fold_origin, then one conditional subtract per pixel: w >= LK_R).
+template <bool WRAP>
 __device__ __forceinline__ void lk_region(uint8_t* Jr, int& rx0, int& ry0, const uint8_t* J, int w, int h, int pitch,
                                           int ix, int iy, int win) {
     const int D = win + 1;
@@ -219,11 +241,13 @@ __device__ __forceinline__ void lk_region(uint8_t* Jr, int& rx0, int& ry0, const
     // every global load of the region is issued before the first LDS store
     constexpr int NR = (LK_R * LK_R + LK_THREADS - 1) / LK_THREADS;
     uint32_t v[NR];
+    const int fx0 = WRAP ? lk_fold_origin(rx0, w) : 0;
 #pragma unroll
     for (int it = 0; it < NR; ++it) {
         const int e = threadIdx.x + LK_THREADS * it;
         const int ty = e / LK_R, tx = e - ty * LK_R;
-        v[it] = e < LK_R * LK_R ? J[(size_t)reflect101(ry0 + ty, h) * pitch + reflect101(rx0 + tx, w)] : 0u;
+        v[it] = e < LK_R * LK_R ? J[(size_t)reflect101(ry0 + ty, h) * pitch +
+                                    (WRAP ? wrap_x(fx0 + tx, w) : reflect101(rx0 + tx, w))] : 0u;
     }
 #pragma unroll
     for (int it = 0; it < NR; ++it) {
@@ -275,6 +299,10 @@ __device__ void lk_aux(const LkAux& X, int b) {
     }
 }
 
+// WRAP (seam wrap mode, A.x_wrap): every level is the periodic continuation of the frame in x -- tile columns
+// modulo the level width, no "left the frame" test in x, the iteration in unwrapped coordinates; only the final
+// next.x is folded into [0, W) by one f32 +-W.  The default instance is the code it was before the mode existed.
+template <bool WRAP>
 __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
     __shared__ LkShared S;
     __shared__ double red[LK_WAVES];
@@ -305,7 +333,7 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
         nxt_x = nx; nxt_y = ny;
         px -= hw; py -= hw;
         const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-        if (ipx < -win || ipx >= w || ipy < -win || ipy >= h) {
+        if ((!WRAP && (ipx < -win || ipx >= w)) || ipy < -win || ipy >= h) {
             if (level == 0) { status = 0; err = 0.f; }
             continue;
         }
@@ -315,11 +343,13 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
         {
             constexpr int NT = (LK_T * LK_T + LK_THREADS - 1) / LK_THREADS;  // loads first, then the LDS stores
             uint32_t v[NT];
+            const int fx0 = WRAP ? lk_fold_origin(ipx - 1, w) : 0;
 #pragma unroll
             for (int it = 0; it < NT; ++it) {
                 const int e = tid + LK_THREADS * it;
                 const int ty = e / T, tx = e - (e / T) * T;
-                v[it] = e < T * T ? I[(size_t)reflect101(ipy - 1 + ty, h) * Lv.pitch + reflect101(ipx - 1 + tx, w)] : 0u;
+                v[it] = e < T * T ? I[(size_t)reflect101(ipy - 1 + ty, h) * Lv.pitch +
+                                      (WRAP ? wrap_x(fx0 + tx, w) : reflect101(ipx - 1 + tx, w))] : 0u;
             }
 #pragma unroll
             for (int it = 0; it < NT; ++it) {
@@ -334,7 +364,7 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
             int ty = e / D, tx = e % D;
             int X = ipx + tx, Y = ipy + ty;
             int gx = 0, gy = 0;
-            if (X >= 0 && Y >= 0 && X < w && Y < h) {
+            if ((WRAP || X >= 0) && Y >= 0 && (WRAP || X < w) && Y < h) {
                 const uint8_t* r0 = &S.It[ty * T + tx];      // (X-1, Y-1)
                 const uint8_t* r1 = r0 + T;
                 const uint8_t* r2 = r1 + T;
@@ -391,13 +421,13 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
         int rx0 = -(1 << 29), ry0 = -(1 << 29);  // no region staged for this level yet
         for (int j = 0; j < A.max_iters; ++j) {
             const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if (inx < -win || inx >= w || iny < -win || iny >= h) {
+            if ((!WRAP && (inx < -win || inx >= w)) || iny < -win || iny >= h) {
                 if (level == 0) status = 0;
                 break;
             }
             a = nx - inx; b = ny - iny;
             lk_weights(a, b, w00, w01, w10, w11);
-            lk_region(S.Jr, rx0, ry0, J, w, h, Lv.pitch, inx, iny, win);
+            lk_region<WRAP>(S.Jr, rx0, ry0, J, w, h, Lv.pitch, inx, iny, win);
             const uint8_t* Jw = S.Jr + (iny - ry0) * LK_R + (inx - rx0);
             int ib1 = 0, ib2 = 0;
 #pragma unroll
@@ -425,11 +455,11 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
         if (status && level == 0) {
             const float fx = nxt_x - hw, fy = nxt_y - hw;
             const int ix = (int)floorf(fx), iy = (int)floorf(fy);
-            if (ix < -win || ix >= w || iy < -win || iy >= h) {
+            if ((!WRAP && (ix < -win || ix >= w)) || iy < -win || iy >= h) {
                 status = 0;
             } else {
                 lk_weights(fx - ix, fy - iy, w00, w01, w10, w11);
-                lk_region(S.Jr, rx0, ry0, J, w, h, Lv.pitch, ix, iy, win);
+                lk_region<WRAP>(S.Jr, rx0, ry0, J, w, h, Lv.pitch, ix, iy, win);
                 const uint8_t* Jw = S.Jr + (iy - ry0) * LK_R + (ix - rx0);
                 long long es = 0;
 #pragma unroll
@@ -444,6 +474,17 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
                 es = wg_sum_i64(es, red);
                 err = (float)es * (1.f / (32 * win * win));
             }
+        }
+    }
+    if (WRAP) {  // fold the tracked column into [0, W): one +-W (exact for a point within one turn of the frame)
+        const float Wf = (float)A.lv[0].w;
+        if (nxt_x < 0.f) nxt_x += Wf;
+        else if (nxt_x >= Wf) nxt_x -= Wf;
+        if (nxt_x == Wf) nxt_x = 0.f;  // (a tiny negative column rounds up to W)
+        if (!(nxt_x >= 0.f && nxt_x < Wf)) {  // more than a turn away, or not a number: the point is lost
+            nxt_x = 0.f;
+            status = 0;
+            err = 0.f;
         }
     }
     if (tid == 0) {
@@ -477,7 +518,8 @@ __device__ void pixel_to_bearing(float u, float v, int W, int H, float* b) {
 // sooner than sixteen while GFTT pass 1 occupies the chip from the side stream):
 //   mode 0: all n points (erp_rot_ransac); mode 1: status ∧ !polar ∧ !boundary (pipeline)
 constexpr int RP_THREADS = 256;
-template <int NT>
+// WRAP: seam wrap mode (R.x_wrap); the default instance is the code as it was
+template <int NT, bool WRAP = false>
 __device__ int ransac_prep_body(const RansacArgs& R, int* wsum, int& base) {
     if (threadIdx.x == 0) base = 0;
     __syncthreads();
@@ -492,10 +534,14 @@ __device__ int ransac_prep_body(const RansacArgs& R, int* wsum, int& base) {
                 float vr = y / (float)R.H;
                 bool polar = (vr < R.polar_ratio) || (vr > (1.0f - R.polar_ratio));
                 float m = (float)R.margin;
-                bool nearb = (x < m) || (x > (float)R.W - m) || (y < m) || (y > (float)R.H - m);
+                // (seam wrap mode: no left / right margin, x is already folded into [0, W))
+                bool nearb = WRAP ? (y < m) || (y > (float)R.H - m)
+                                  : (x < m) || (x > (float)R.W - m) || (y < m) || (y > (float)R.H - m);
                 good = R.status[i] && !polar && !nearb;
                 if (R.excl_bits && good) {  // region mask: the pixel the point rounds to (as the disc centres)
-                    const int xi = (int)rintf(x), yi = (int)rintf(y);
+                    int xi = (int)rintf(x);
+                    const int yi = (int)rintf(y);
+                    if (WRAP && xi == R.W) xi = 0;  // a column within half a pixel of the seam rounds across it
                     good = (unsigned)xi < (unsigned)R.W && (unsigned)yi < (unsigned)R.H &&
                            !((R.excl_bits[(size_t)yi * R.excl_words + (xi >> 5)] >> (xi & 31)) & 1u);
                 }
@@ -685,7 +731,7 @@ __global__ void __launch_bounds__(RS_THREADS) ransac_raw_kernel(uint32_t seed, u
 constexpr int RS_SAMPLE_THREADS = 256;
 constexpr int RS_CHUNK = 20;
 static_assert(RS_CHUNK % 4 == 0 && RS_RAW % 4 == 0 && RS_SAMPLE_THREADS * RS_CHUNK >= RS_RAW, "sampler chunks");
-template <bool PREP>
+template <bool PREP, bool WRAP = false>
 __global__ void __launch_bounds__(RS_SAMPLE_THREADS) ransac_sample_kernel(RansacArgs R) {
     __shared__ uint32_t acc[RS_RAW];    // accepted draws (compacted), in stream order
     __shared__ uint8_t len3[RS_RAW];    // 1: a hypothesis starting at draw p consumes exactly 3 draws
@@ -694,7 +740,7 @@ __global__ void __launch_bounds__(RS_SAMPLE_THREADS) ransac_sample_kernel(Ransac
 #ifdef TRK_STAMPS
     const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-    const int n = PREP ? ransac_prep_body<RS_SAMPLE_THREADS>(R, wsum, s_base) : *R.n_good;
+    const int n = PREP ? ransac_prep_body<RS_SAMPLE_THREADS, WRAP>(R, wsum, s_base) : *R.n_good;
 #ifdef TRK_STAMPS
     const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -966,7 +1012,8 @@ struct GfTile {
 
 __device__ __forceinline__ bool gf_masked_in(const GfArgs& G, int x, int y) {
     if (G.mask) return G.mask[(size_t)y * G.mask_pitch + x] != 0;
-    if (y < G.top_rows || y >= G.bottom_start || x < G.margin || x >= G.W - G.margin) return false;
+    if (y < G.top_rows || y >= G.bottom_start) return false;
+    if (!G.x_wrap && (x < G.margin || x >= G.W - G.margin)) return false;  // (seam wrap mode: no side margins)
     if (G.disc_bits) {
         uint32_t wbits = G.disc_bits[(size_t)y * G.disc_words + (x >> 5)];
         if ((wbits >> (x & 31)) & 1u) return false;
@@ -996,7 +1043,8 @@ __device__ void gf_eig_tile(const GfArgs& G, int ex0, int ey0, uint8_t (*src)[Gf
         for (int it = 0; it < NS; ++it) {
             const int e = threadIdx.x + 256 * it;
             const int ty = e / T::SW, tx = e % T::SW;
-            v[it] = e < T::SW * T::SH ? G.img[(size_t)reflect101(sy0 + ty, H) * G.pitch + reflect101(sx0 + tx, W)] : 0u;
+            v[it] = e < T::SW * T::SH
+                        ? G.img[(size_t)reflect101(sy0 + ty, H) * G.pitch + border_x(sx0 + tx, W, G.x_wrap)] : 0u;
         }
 #pragma unroll
         for (int it = 0; it < NS; ++it) {
@@ -1027,9 +1075,12 @@ __device__ void gf_eig_tile(const GfArgs& G, int ex0, int ey0, uint8_t (*src)[Gf
     } else
     for (int e = threadIdx.x; e < T::CW * T::CH; e += 256) {
         int cy = e / T::CW, cx = e % T::CW;
-        int X = reflect101(ex0 - 1 + cx, W), Y = reflect101(ey0 - 1 + cy, H);
+        int X = border_x(ex0 - 1 + cx, W, G.x_wrap), Y = reflect101(ey0 - 1 + cy, H);
         // tile coordinates of X-1, X, X+1 (reflected about the image) — map back into the tile
         int xm = reflect101(X - 1, W) - sx0, xc = X - sx0, xp = reflect101(X + 1, W) - sx0;
+        // seam wrap mode: the tile's columns are those of the periodic continuation, so the neighbours of the cov
+        // position in tile column cx + 1 are its neighbours in the tile
+        if (G.x_wrap) { xm = cx; xc = cx + 1; xp = cx + 2; }
         int ym = reflect101(Y - 1, H) - sy0, yc = Y - sy0, yp = reflect101(Y + 1, H) - sy0;
         int sx, sy;
         if (xm >= 0 && xp < T::SW && ym >= 0 && yp < T::SH && xc >= 0 && xc < T::SW && yc >= 0 && yc < T::SH) {
@@ -1042,7 +1093,7 @@ __device__ void gf_eig_tile(const GfArgs& G, int ex0, int ey0, uint8_t (*src)[Gf
             const uint8_t* r0 = G.img + (size_t)reflect101(Y - 1, H) * G.pitch;
             const uint8_t* r1 = G.img + (size_t)Y * G.pitch;
             const uint8_t* r2 = G.img + (size_t)reflect101(Y + 1, H) * G.pitch;
-            int gxm = reflect101(X - 1, W), gxp = reflect101(X + 1, W);
+            int gxm = border_x(X - 1, W, G.x_wrap), gxp = border_x(X + 1, W, G.x_wrap);
             sx = (r0[gxp] - r0[gxm]) + 2 * (r1[gxp] - r1[gxm]) + (r2[gxp] - r2[gxm]);
             sy = (r2[gxm] + 2 * r2[X] + r2[gxp]) - (r0[gxm] + 2 * r0[X] + r0[gxp]);
         }
@@ -1070,10 +1121,11 @@ __device__ void gf_eig_tile(const GfArgs& G, int ex0, int ey0, uint8_t (*src)[Gf
         } else {
             // border pixel: neighbours reflect about the image; cov positions of (X+k) live at
             // tile index reflect101(X+k) - (ex0-1), valid for every in-image X of this tile
+            // (seam wrap mode: the cov columns continue periodically, X + k lives at its own tile column)
             for (int ky = -1; ky <= 1; ++ky) {
                 int yy = reflect101(Y + ky, H) - (ey0 - 1);
                 for (int kx = -1; kx <= 1; ++kx) {
-                    int xx = reflect101(X + kx, W) - (ex0 - 1);
+                    int xx = (G.x_wrap ? X + kx : reflect101(X + kx, W)) - (ex0 - 1);
                     const float* c = cov[yy][xx];
                     s0 += c[0]; s1 += c[1]; s2 += c[2];
                 }
@@ -1162,6 +1214,9 @@ __global__ void __launch_bounds__(256) gftt_cand_kernel(GfArgs G) {
             const int e = threadIdx.x + 256 * it;
             const int ey = e / T::EW, ex = e % T::EW;
             const int X = blockIdx.x * GF_BX - 1 + ex, Y = (blockIdx.y * GF_SUB + sub) * GF_BY - 1 + ey;
+            // (seam wrap mode: the halo columns are the map's columns across the seam)
+            if (G.x_wrap) vmap[sub][it] = (e < T::EW * T::EH && Y >= 0 && Y < G.H) ? G.eig[(size_t)Y * G.W + wrap_x(X, G.W)] : 0.f;
+            else
             vmap[sub][it] = (e < T::EW * T::EH && X >= 0 && Y >= 0 && X < G.W && Y < G.H)
                                 ? G.eig[(size_t)Y * G.W + X] : 0.f;
         }
@@ -1183,7 +1238,7 @@ __global__ void __launch_bounds__(256) gftt_cand_kernel(GfArgs G) {
             int X = ox + tx, Y = oy + ty;
             bool c = false;
             float v = 0.f;
-            if (X >= 1 && X < G.W - 1 && Y >= 1 && Y < G.H - 1) {
+            if ((G.x_wrap ? X < G.W : (X >= 1 && X < G.W - 1)) && Y >= 1 && Y < G.H - 1) {
                 v = eig[ty + 1][tx + 1];
                 if (v != 0.f && gf_masked_in(G, X, Y)) {
                     float m = v;
@@ -1240,8 +1295,12 @@ constexpr int GS_SLOTS = 3;
 // exact tail by construction (the same keys in the same order reach the greedy pass).  The prefix is staged
 // GS_STAGE keys at a time: their disc / threshold tests run in parallel (two memory round trips per stage
 // instead of per batch) and the batches are formed from the staged survivors only.
+// WRAP (seam wrap mode, G.x_wrap): the distance is taken on the cylinder, min(|dx|, W - |dx|)^2 + dy^2, and the
+// neighbour cells continue across the seam.  |dx| <= cell for every conflicting pair, and the last cell column is
+// partial when W % cell != 0, so the columns of x - cell .. x + cell are the cell's own and two on either side
+// (a column met twice in a narrow grid only repeats a test).  The default instances are the code as it was.
 constexpr int GS_STAGE = 4 * GS_THREADS;
-template <bool GLOBAL_GRID, bool HASH>
+template <bool GLOBAL_GRID, bool HASH, bool WRAP = false>
 __global__ void __launch_bounds__(GS_THREADS) gftt_select_kernel(GfArgs G, const unsigned long long* keys,
                                                                   const unsigned int* n_keys, unsigned int cap,
                                                                   int fast) {
@@ -1301,19 +1360,32 @@ __global__ void __launch_bounds__(GS_THREADS) gftt_select_kernel(GfArgs G, const
     const unsigned int total = min(*n_keys, cap);
     const int cell = G.cell;
     const double md2 = G.min_dist * G.min_dist;
+    constexpr int NX = WRAP ? 2 : 1;  // neighbour cell columns on either side
+    const float Wf = (float)G.W;
+    auto seam_dx = [&](float ddx) {  // WRAP: the shorter way round
+        if (WRAP) {
+            ddx = fabsf(ddx);
+            ddx = fminf(ddx, Wf - ddx);
+        }
+        return ddx;
+    };
+    auto cell_col = [&](int xx) {  // WRAP: the cell column across the seam (gw >= 2)
+        if (WRAP) xx = xx < 0 ? xx + G.gw : (xx >= G.gw ? xx - G.gw : xx);
+        return xx;
+    };
     auto conflicts = [&](int x, int y, int slot_lane_only) -> bool {
         const int xc = x / cell, yc = y / cell;
         bool hit = false;
 #pragma unroll
         for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int xx = xc + dx, yy = yc + dy;
+            for (int dx = -NX; dx <= NX; ++dx) {
+                const int xx = cell_col(xc + dx), yy = yc + dy;
                 if (xx < 0 || yy < 0 || xx >= G.gw || yy >= G.gh) continue;
 #pragma unroll
                 for (int s = 0; s < GS_SLOTS; ++s) {  // every slot read (independent loads), empty = 0xffffffff
                     const uint32_t p = grid[(yy * G.gw + xx) * GS_SLOTS + s];
-                    const float ddx = (float)x - (float)(p & 0xffffu), ddy = (float)y - (float)(p >> 16);
+                    const float ddx = seam_dx((float)x - (float)(p & 0xffffu)), ddy = (float)y - (float)(p >> 16);
                     hit |= p != 0xffffffffu && (double)(ddx * ddx + ddy * ddy) < md2;
                 }
             }
@@ -1438,13 +1510,13 @@ __global__ void __launch_bounds__(GS_THREADS) gftt_select_kernel(GfArgs G, const
                 for (int q = 0; q < GS_THREADS / 64; ++q) m[q] = 0ull;
                 const int xc = x / cell, yc = y / cell;
                 for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const int xx = xc + dx, yy = yc + dy;
+                    for (int dx = -NX; dx <= NX; ++dx) {
+                        const int xx = cell_col(xc + dx), yy = yc + dy;
                         if (xx < 0 || yy < 0 || xx >= G.gw || yy >= G.gh) continue;
                         for (int bq = head[yy * G.gw + xx]; bq >= 0; bq = s_next[bq]) {
                             if (bq >= rank) continue;
                             const unsigned int pj = s_sv[bq];
-                            const float ddx = (float)x - (float)(pj & 0xffff), ddy = (float)y - (float)(pj >> 16);
+                            const float ddx = seam_dx((float)x - (float)(pj & 0xffff)), ddy = (float)y - (float)(pj >> 16);
                             if ((double)(ddx * ddx + ddy * ddy) < md2) m[bq >> 6] |= 1ull << (bq & 63);
                         }
                     }
@@ -1459,7 +1531,7 @@ __global__ void __launch_bounds__(GS_THREADS) gftt_select_kernel(GfArgs G, const
 #pragma unroll 8
                     for (int b = 0; b < jend; ++b) {
                         const unsigned int pj = s_sv[64 * q + b];
-                        const float ddx = (float)x - (float)(pj & 0xffff), ddy = (float)y - (float)(pj >> 16);
+                        const float ddx = seam_dx((float)x - (float)(pj & 0xffff)), ddy = (float)y - (float)(pj >> 16);
                         if ((double)(ddx * ddx + ddy * ddy) < md2) m |= 1ull << b;
                     }
                     s_conf[rank][q] = m;
@@ -1734,36 +1806,53 @@ hipError_t launch_gftt_reset(const GfArgs& g, int* scal, hipStream_t st) {
 
 // rasterise the discs of CreateFeatureMask (cv::circle filled, LINE_8; half-widths precomputed
 // on the host from OpenCV's midpoint Circle()) into a 1-bit-per-pixel exclusion mask
+// the bits of columns [x0, x1] (inside the frame) of row y
+__device__ __forceinline__ void disc_span(const DiscArgs& D, int y, int x0, int x1) {
+    for (int x = x0; x <= x1;) {
+        int wi = x >> 5;
+        int b0 = x & 31;
+        int b1 = min(31, x1 - (wi << 5));
+        uint32_t m = (b1 - b0 == 31) ? 0xffffffffu : (((1u << (b1 - b0 + 1)) - 1u) << b0);
+        atomicOr(&D.bits[(size_t)y * D.words + wi], m);
+        x = (wi + 1) << 5;
+    }
+}
+template <bool WRAP>
 __device__ __forceinline__ void disc_raster(const DiscArgs& D, int i, int nthreads) {
     const float fx = D.pts[2 * i], fy = D.pts[2 * i + 1];
     const int cx = (int)rintf(fx), cy = (int)rintf(fy);  // Point2f -> Point (cvRound)
     const int r = D.radius;
+    // seam wrap mode: the columns are taken modulo W -- a span that leaves the frame on one side continues on the
+    // other (radius < W / 2: the two parts never meet); a centre further than W outside draws nothing
+    if (WRAP && (cx < -D.W || cx >= 2 * D.W)) return;
     for (int dy = -r + (int)threadIdx.x; dy <= r; dy += nthreads) {
         int y = cy + dy;
         if (y < 0 || y >= D.H) continue;
         int hwd = D.halfw[dy < 0 ? -dy : dy];
-        int x0 = max(cx - hwd, 0), x1 = min(cx + hwd, D.W - 1);
-        for (int x = x0; x <= x1;) {
-            int wi = x >> 5;
-            int b0 = x & 31;
-            int b1 = min(31, x1 - (wi << 5));
-            uint32_t m = (b1 - b0 == 31) ? 0xffffffffu : (((1u << (b1 - b0 + 1)) - 1u) << b0);
-            atomicOr(&D.bits[(size_t)y * D.words + wi], m);
-            x = (wi + 1) << 5;
+        if (WRAP) {
+            const int c = cx < 0 ? cx + D.W : (cx >= D.W ? cx - D.W : cx);
+            const int a = c - hwd, b = c + hwd;
+            disc_span(D, y, max(a, 0), min(b, D.W - 1));
+            if (a < 0) disc_span(D, y, max(a + D.W, 0), D.W - 1);
+            if (b >= D.W) disc_span(D, y, 0, min(b - D.W, D.W - 1));
+            continue;
         }
+        disc_span(D, y, max(cx - hwd, 0), min(cx + hwd, D.W - 1));
     }
 }
+template <bool WRAP>
 __global__ void __launch_bounds__(128) disc_mask_kernel(DiscArgs D) {
     const int k = blockIdx.x;
     if (D.n_pts_dev && k >= *D.n_pts_dev) return;  // null: the grid is exactly the point count
     if (D.kept && !D.kept[D.src_index ? D.src_index[k] : k]) return;
-    disc_raster(D, D.src_index ? D.src_index[k] : k, 128);
+    disc_raster<WRAP>(D, D.src_index ? D.src_index[k] : k, 128);
 }
 
 // tracker pipeline: RANSAC's selection and CreateFeatureMask's discs in one launch (one launch fewer on the
 // critical path).  Workgroup j (compacted point j < n_good; the grid covers every input point) finds the best
 // hypothesis itself -- the same reduction in every workgroup -- tests its point, scatters the kept flag and,
 // when kept, rasterises the point's disc (disc_mask_kernel's rows; D.radius <= 0: no discs)
+template <bool WRAP>
 __global__ void __launch_bounds__(256) ransac_select_disc_kernel(RansacArgs R, DiscArgs D) {
     __shared__ int sbest[256], sidx[256];
     __shared__ float Rs[9];
@@ -1780,7 +1869,7 @@ __global__ void __launch_bounds__(256) ransac_select_disc_kernel(RansacArgs R, D
         s_m = m;
     }
     __syncthreads();
-    if (s_m && D.radius > 0) disc_raster(D, R.gidx[j], 256);
+    if (s_m && D.radius > 0) disc_raster<WRAP>(D, R.gidx[j], 256);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2246,7 +2335,8 @@ __global__ void __launch_bounds__(256) gftt_lm_flatten_kernel(GfArgs G) {
 hipError_t launch_pyr_down(const PyrLevelPair& s, const PyrLevelPair& d, int frames, hipStream_t st) {
     constexpr int by = 8;
     dim3 g((d.w + PD_BX - 1) / PD_BX, (d.h + by - 1) / by, frames);
-    hipLaunchKernelGGL(pyr_down_kernel<by>, g, dim3(256), 0, st, s, d);
+    if (s.x_wrap) hipLaunchKernelGGL((pyr_down_kernel<by, true>), g, dim3(256), 0, st, s, d);
+    else hipLaunchKernelGGL(pyr_down_kernel<by>, g, dim3(256), 0, st, s, d);
     return hipGetLastError();
 }
 hipError_t launch_lk(const LkArgs& a, hipStream_t st, const LkAux* aux) {
@@ -2255,7 +2345,8 @@ hipError_t launch_lk(const LkArgs& a, hipStream_t st, const LkAux* aux) {
     if (aux) x = *aux;
     const int n = a.n > 0 ? a.n : 0, blocks = n + (aux ? LK_AUX_BLOCKS : 0);
     if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(lk_kernel, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
+    if (a.x_wrap) hipLaunchKernelGGL(lk_kernel<true>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
+    else hipLaunchKernelGGL(lk_kernel<false>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
     return hipGetLastError();
 }
 size_t ransac_raw_words() { return RS_RAW; }
@@ -2275,14 +2366,17 @@ hipError_t launch_ransac(const RansacArgs& r, bool gen_samples, hipStream_t st) 
     return hipGetLastError();
 }
 hipError_t launch_ransac_pipeline(const RansacArgs& r, const DiscArgs& d, hipStream_t st) {
-    hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
+    if (r.x_wrap) hipLaunchKernelGGL((ransac_sample_kernel<true, true>), dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
+    else hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
     if (r.iters > 0) hipLaunchKernelGGL(ransac_hyp_kernel, dim3((r.iters + 3) / 4), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(ransac_select_disc_kernel, dim3(r.n > 0 ? r.n : 1), dim3(256), 0, st, r, d);
+    if (d.x_wrap) hipLaunchKernelGGL(ransac_select_disc_kernel<true>, dim3(r.n > 0 ? r.n : 1), dim3(256), 0, st, r, d);
+    else hipLaunchKernelGGL(ransac_select_disc_kernel<false>, dim3(r.n > 0 ? r.n : 1), dim3(256), 0, st, r, d);
     return hipGetLastError();
 }
 hipError_t launch_disc_mask(const DiscArgs& d, int max_pts, hipStream_t st) {
     if (max_pts <= 0) return hipSuccess;
-    hipLaunchKernelGGL(disc_mask_kernel, dim3(max_pts), dim3(128), 0, st, d);
+    if (d.x_wrap) hipLaunchKernelGGL(disc_mask_kernel<true>, dim3(max_pts), dim3(128), 0, st, d);
+    else hipLaunchKernelGGL(disc_mask_kernel<false>, dim3(max_pts), dim3(128), 0, st, d);
     return hipGetLastError();
 }
 hipError_t launch_gftt_eig(const GfArgs& g, hipStream_t st) {
@@ -2307,7 +2401,15 @@ static hipError_t launch_select(const GfArgs& g, const unsigned long long* keys,
                                 unsigned int cap, int fast, hipStream_t st) {
     const bool hash = gftt_select_lds(g, true) <= GF_SELECT_LDS_MAX;
     const size_t lds = gftt_select_lds(g, hash);
-    if (g.grid_global) {
+    if (g.x_wrap) {  // seam wrap mode
+        if (g.grid_global) {
+            if (hash) hipLaunchKernelGGL((gftt_select_kernel<true, true, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
+            else hipLaunchKernelGGL((gftt_select_kernel<true, false, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
+        } else {
+            if (hash) hipLaunchKernelGGL((gftt_select_kernel<false, true, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
+            else hipLaunchKernelGGL((gftt_select_kernel<false, false, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
+        }
+    } else if (g.grid_global) {
         if (hash) hipLaunchKernelGGL((gftt_select_kernel<true, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
         else hipLaunchKernelGGL((gftt_select_kernel<true, false>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
     } else {
@@ -2465,8 +2567,12 @@ hipError_t gftt_select_set_lds(size_t bytes) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (bytes <= cur[dev]) return hipSuccess;
-    const void* fns[4] = {(const void*)gftt_select_kernel<false, false>, (const void*)gftt_select_kernel<false, true>,
-                          (const void*)gftt_select_kernel<true, false>, (const void*)gftt_select_kernel<true, true>};
+    const void* fns[8] = {(const void*)gftt_select_kernel<false, false>, (const void*)gftt_select_kernel<false, true>,
+                          (const void*)gftt_select_kernel<true, false>, (const void*)gftt_select_kernel<true, true>,
+                          (const void*)gftt_select_kernel<false, false, true>,
+                          (const void*)gftt_select_kernel<false, true, true>,
+                          (const void*)gftt_select_kernel<true, false, true>,
+                          (const void*)gftt_select_kernel<true, true, true>};
     for (const void* f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;

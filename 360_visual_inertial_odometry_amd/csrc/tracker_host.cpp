@@ -89,6 +89,7 @@ struct erp_tracker {
     uint32_t* d_static = nullptr;
     bool has_mask = false;
     uint8_t* d_usable = nullptr;
+    int seam = VIO_SEAM_CUT;  // erp_tracker_set_seam: VIO_SEAM_WRAP runs every stage on the periodic continuation
     // GFTT top-K fast path
     unsigned int* d_hist = nullptr;
     unsigned long long *d_topk = nullptr, *d_topk_sorted = nullptr;
@@ -259,6 +260,20 @@ int tracker_alloc(erp_tracker* t) {
     return VIO_OK;
 }
 
+// the same walk on the sizes alone (tracker_alloc's levels), for erp_seam_check: the top level and its width
+int lk_top_level_of(int W, int H, int win, int max_level, int* top_w) {
+    int w = W, h = H, lvl = 0;
+    for (int l = 0; l <= max_level && l < TRK_MAX_LEVELS; ++l) {
+        lvl = l;
+        *top_w = w;
+        if (w <= 2 || h <= 2) break;  // the last level tracker_alloc makes
+        const int nw = (w + 1) / 2, nh = (h + 1) / 2;
+        if (nw <= win || nh <= win || l + 1 >= TRK_MAX_LEVELS) break;
+        w = nw; h = nh;
+    }
+    return lvl;
+}
+
 // top LK level: buildOpticalFlowPyramid stops when the next level would be <= winSize
 int lk_top_level(const erp_tracker* t, int win, int max_level) {
     int lvl = 0;
@@ -272,8 +287,8 @@ int lk_top_level(const erp_tracker* t, int win, int max_level) {
 
 int build_pyramids(erp_tracker* t, int top) {
     for (int l = 1; l <= top; ++l) {
-        PyrLevelPair s{t->lvl[0][l - 1], t->lvl[1][l - 1], t->lw[l - 1], t->lh[l - 1], t->lp[l - 1]};
-        PyrLevelPair d{t->lvl[0][l], t->lvl[1][l], t->lw[l], t->lh[l], t->lp[l]};
+        PyrLevelPair s{t->lvl[0][l - 1], t->lvl[1][l - 1], t->lw[l - 1], t->lh[l - 1], t->lp[l - 1], t->seam};
+        PyrLevelPair d{t->lvl[0][l], t->lvl[1][l], t->lw[l], t->lh[l], t->lp[l], t->seam};
         hipError_t e = launch_pyr_down(s, d, 2, t->ctx->stream);
         if (e != hipSuccess) return hip_fail(t->ctx, e, "pyr_down_kernel");
     }
@@ -310,6 +325,7 @@ int enqueue_lk(erp_tracker* t, const erp_klt_params* p, int n, bool pyr_built = 
     double eps = std::min(std::max((double)p->epsilon, 0.0), 10.0);
     a.eps2 = eps * eps;
     a.min_eig = p->min_eig_threshold;
+    a.x_wrap = t->seam;
     if (aux) a.bear1 = t->d_bear1;  // the pipeline's RANSAC input (its previous points' bearings: aux workgroups)
     if (t->ev[1] && (!aux || t->stage_timing)) (void)hipEventRecord(t->ev[1], t->ctx->stream);
     hipError_t e = launch_lk(a, t->ctx->stream, aux);
@@ -326,6 +342,7 @@ RansacArgs ransac_args(erp_tracker* t, int n, int mode, int iters, uint32_t seed
     r.polar_ratio = polar; r.margin = margin;
     r.excl_bits = mode == 1 && t->has_mask ? t->d_static : nullptr;
     r.excl_words = t->disc_words;
+    r.x_wrap = t->seam;
     r.gidx = t->d_gidx; r.n_good = t->d_scal + 0;
     r.b0 = t->d_b0; r.b1 = t->d_b1;
     r.samples = t->d_samples; r.iters = iters; r.seed = seed; r.thresh = thr;
@@ -397,7 +414,10 @@ int enqueue_gftt(erp_tracker* t, const uint8_t* img, int pitch, const uint8_t* m
     g.img = img; g.W = t->W; g.H = t->H; g.pitch = pitch;
     g.mask = mask; g.mask_pitch = mask_pitch;
     gf_static_region(t, margin, polar, g);
-    if (!mask) gf_lmax_fields(t, g);  // analytic mask: the local-maximum path
+    // analytic mask: the local-maximum path; seam wrap mode takes the map path with the analytic mask instead
+    // (eigenvalue map, masked maximum, candidates: the kernels that know the periodic continuation)
+    g.x_wrap = t->seam;
+    if (!mask && !t->seam) gf_lmax_fields(t, g);
     // the exclusion plane: the discs stamped onto the region mask's plane, the mask's plane alone, or none
     g.disc_bits = discs ? t->d_disc : (t->has_mask ? t->d_static : nullptr);
     g.disc_words = t->disc_words;
@@ -677,7 +697,9 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
         const char* v = std::getenv("VIO_TRK_PRESEL");
         return !(v && v[0] == '0');
     }();
-    const bool presel = presel_env;
+    // seam wrap mode: detection takes the exact route on the main stream (enqueue_gftt's map path), no side work
+    const bool wrap = t->seam != VIO_SEAM_CUT;
+    const bool presel = presel_env && !wrap;
     // the presort reaches the greedy pass through a device counter (VIO_TRK_PRESEL_FLAG=0: through the stream
     // join, ~6-14 us of event latency on the critical path); a captured graph keeps the join (the counter's
     // target is per run)
@@ -739,16 +761,16 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
         x.W = t->W;
         x.H = t->H;
         int top = lk_top_level(t, klt->win, klt->max_level);
-        if (side_env == 2) {
+        if (side_env == 2 && !wrap) {
             VIO_HIP(t->ctx, hipEventRecord(t->pyr_done, st));
             if ((rc = enqueue_side())) return rc;
         }
         if ((rc = build_pyramids(t, top))) return rc;
-        if (side_env != 2) VIO_HIP(t->ctx, hipEventRecord(t->pyr_done, st));
-        if (side_env == 1 && (rc = enqueue_side())) return rc;
+        if (side_env != 2 && !wrap) VIO_HIP(t->ctx, hipEventRecord(t->pyr_done, st));
+        if (side_env == 1 && !wrap && (rc = enqueue_side())) return rc;
         if ((rc = enqueue_lk(t, klt, n, true, &x))) return rc;
     }
-    if (side_env == 0 && (rc = enqueue_side())) return rc;
+    if (side_env == 0 && !wrap && (rc = enqueue_side())) return rc;
     if (t->stage_timing) VIO_HIP(t->ctx, hipEventRecord(t->ev[2], st));
     RansacArgs r = ransac_args(t, n, 1, p->ransac_iters, p->ransac_seed, p->ransac_thresh_rad, p->polar_ratio,
                                p->boundary_margin, t->d_pts, t->d_next);
@@ -758,16 +780,16 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
         // RANSAC, then its selection and CreateFeatureMask's discs of radius (int)min_dist around every kept
         // point in one launch (bitmap cleared in the LK launch; radius 0: no discs)
         DiscArgs d{t->d_next, t->d_kept, nullptr, nullptr, t->d_disc, t->disc_words, t->W, t->H, radius,
-                   t->d_halfw};
+                   t->d_halfw, t->seam};
         hipError_t e = launch_ransac_pipeline(r, d, st);
         if (e != hipSuccess) return hip_fail(t->ctx, e, "ransac kernels");
     } else {
         VIO_HIP(t->ctx, hipMemsetAsync(t->d_scal, 0, 2 * sizeof(int), st));
     }
     if (t->stage_timing) VIO_HIP(t->ctx, hipEventRecord(t->ev[3], st));
-    if (!t->presel_flag) VIO_HIP(t->ctx, hipStreamWaitEvent(st, t->join, 0));
+    if (!t->presel_flag && !wrap) VIO_HIP(t->ctx, hipStreamWaitEvent(st, t->join, 0));
     if ((rc = enqueue_gftt(t, t->lvl[1][0], t->lp[0], nullptr, 0, p->max_corners, p->quality, p->min_dist, true,
-                           p->boundary_margin, p->polar_ratio, true, true, presel)))
+                           p->boundary_margin, p->polar_ratio, !wrap, true, presel)))
         return rc;
     return VIO_OK;
 }
@@ -780,6 +802,10 @@ int erp_tracker_run(erp_tracker* t, const erp_klt_params* klt, const erp_tracker
     if (p->ransac_iters < 0 || p->max_corners < 0 || p->max_corners > t->max_corners || p->quality <= 0 ||
         p->min_dist < 0) {
         set_error(t->ctx, "bad erp_tracker_params");
+        return VIO_EINVAL;
+    }
+    if (t->seam != VIO_SEAM_CUT && erp_seam_check(t->W, t->H, klt->win, klt->max_level, p->min_dist) != VIO_OK) {
+        set_error(t->ctx, "erp_tracker_run: the frame size, LK levels or min_dist do not admit VIO_SEAM_WRAP (erp_seam_check)");
         return VIO_EINVAL;
     }
     VIO_DEVICE(t->ctx);
@@ -888,14 +914,47 @@ int erp_tracker_stage_ms(erp_tracker* t, double* pyr_ms, double* lk_ms, double* 
     return VIO_OK;
 }
 
+int erp_seam_check(int W, int H, int win, int max_level, double min_dist) {
+    if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || win <= 2 || win > LK_WIN_MAX || max_level < 0 ||
+        max_level >= TRK_MAX_LEVELS || !(min_dist >= 0))
+        return VIO_EINVAL;
+    int top_w = W;
+    const int top = lk_top_level_of(W, H, win, max_level, &top_w);
+    if (W % (1 << top) != 0) return VIO_EINVAL;     // an odd level: its wrapped pyrDown is not the continuation's
+    static_assert(LK_R >= LK_T, "the next-frame region is the wider LK staging tile");
+    if (top_w < LK_R) return VIO_EINVAL;            // a staging tile would cross the seam twice
+    if ((double)W <= 2.0 * min_dist) return VIO_EINVAL;  // a disc / min-distance neighbourhood would meet itself
+    return VIO_OK;
+}
+
+static int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who) {
+    if (seam != VIO_SEAM_CUT && seam != VIO_SEAM_WRAP) {
+        set_error(ctx, std::string(who) + ": unknown seam mode");
+        return VIO_EINVAL;
+    }
+    if (seam == VIO_SEAM_WRAP && erp_seam_check(W, H, win, max_level, min_dist) != VIO_OK) {
+        set_error(ctx, std::string(who) + ": the frame size, LK levels or min_dist do not admit VIO_SEAM_WRAP (erp_seam_check)");
+        return VIO_EINVAL;
+    }
+    return VIO_OK;
+}
+
 int erp_klt_track(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride, const float* pts,
                   int n, float* next, uint8_t* status, float* err, const erp_klt_params* params) {
+    return erp_klt_track_seam(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, VIO_SEAM_CUT);
+}
+
+int erp_klt_track_seam(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                       const float* pts, int n, float* next, uint8_t* status, float* err, const erp_klt_params* params,
+                       int seam) {
     if (!ctx || !prev || !curr || n < 0 || (n > 0 && (!pts || !next || !status))) return VIO_EINVAL;
     int rc = check_klt(ctx, params);
     if (rc) return rc;
+    if ((rc = seam_mode_ok(ctx, seam, W, H, params->win, params->max_level, 0.0, "erp_klt_track_seam"))) return rc;
     VIO_DEVICE(ctx);
     erp_tracker* t = nullptr;
     if ((rc = erp_tracker_create(ctx, W, H, std::max(n, 1), 0, &t))) return rc;
+    t->seam = seam;
     if (!(rc = upload_frame(t, 0, prev, stride)) && !(rc = upload_frame(t, 1, curr, stride)) &&
         !(rc = erp_tracker_set_points(t, pts, n)) && !(rc = enqueue_lk(t, params, n))) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -913,12 +972,20 @@ int erp_klt_track(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W,
 
 int erp_gftt(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H, int stride, int max_corners,
              double quality, double min_dist, float* out_xy, int* n_out) {
+    return erp_gftt_seam(ctx, img, mask, W, H, stride, max_corners, quality, min_dist, out_xy, n_out, VIO_SEAM_CUT);
+}
+
+int erp_gftt_seam(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H, int stride, int max_corners,
+                  double quality, double min_dist, float* out_xy, int* n_out, int seam) {
     if (!ctx || !img || !n_out || W < 3 || H < 3 || quality <= 0 || min_dist < 0 || max_corners < 0) return VIO_EINVAL;
+    int rc = seam_mode_ok(ctx, seam, W, H, 3, 0, min_dist, "erp_gftt_seam");
+    if (rc) return rc;
     if (max_corners == 0) max_corners = W * H;  // "no limit"
     VIO_DEVICE(ctx);
     erp_tracker* t = nullptr;
-    int rc = tracker_new(ctx, W, H, 1, max_corners, 3, &t);  // down to the W, H >= 3 checked above
+    rc = tracker_new(ctx, W, H, 1, max_corners, 3, &t);  // down to the W, H >= 3 checked above
     if (rc) return rc;
+    t->seam = seam;
     uint8_t* dmask = nullptr;
     if (!(rc = upload_frame(t, 1, img, stride))) {
         if (mask) {
@@ -1059,6 +1126,7 @@ struct erp_frontend {
     int num_tracked = 0, num_detected = 0;
     std::vector<FeatureRec> feats;
     erp_equalize_params eq{};  // erp_frontend_set_equalize; mode VIO_EQ_NONE: off
+    int seam = VIO_SEAM_CUT;   // erp_frontend_set_seam (the tracker's mode follows it)
 };
 
 namespace {
@@ -1085,7 +1153,8 @@ int frontend_detect(erp_frontend* f, std::vector<float>& corners) {
             VIO_HIP(t->ctx, hipMemcpy(t->d_halfw, hw.data(), sizeof(int) * (radius + 1), hipMemcpyHostToDevice));
             t->halfw_r = radius;
         }
-        DiscArgs d{t->d_pts, nullptr, nullptr, nullptr, t->d_disc, t->disc_words, t->W, t->H, radius, t->d_halfw};
+        DiscArgs d{t->d_pts, nullptr, nullptr, nullptr, t->d_disc, t->disc_words, t->W, t->H, radius, t->d_halfw,
+                   t->seam};
         hipError_t e = launch_disc_mask(d, n, st);
         if (e != hipSuccess) return hip_fail(t->ctx, e, "disc_mask_kernel");
     }
@@ -1158,7 +1227,7 @@ static int frontend_track_slot1(erp_frontend* f, int* n_features) {
         VIO_HIP(ctx, hipMemcpyAsync(status.data(), t->d_status, n, hipMemcpyDeviceToHost, st));
         if (t->has_mask) {  // the region mask's bit under every tracked point, gathered on the device
             usable.resize(n);
-            VIO_HIP(ctx, launch_mask_gather(t->d_next, n, t->d_static, t->W, t->H, t->d_usable, st));
+            VIO_HIP(ctx, launch_mask_gather(t->d_next, n, t->d_static, t->W, t->H, t->d_usable, st, f->seam));
             VIO_HIP(ctx, hipMemcpyAsync(usable.data(), t->d_usable, n, hipMemcpyDeviceToHost, st));
         }
         VIO_HIP(ctx, hipStreamSynchronize(st));
@@ -1169,7 +1238,8 @@ static int frontend_track_slot1(erp_frontend* f, int* n_features) {
             float x = next[2 * i], y = next[2 * i + 1];
             float vr = y / (float)f->H;
             bool polar = vr < 0.15f || vr > (1.0f - 0.15f);
-            bool nearb = x < m || x > (float)f->W - m || y < m || y > (float)f->H - m;
+            // (seam wrap mode: no left / right margin, x is folded into [0, W))
+            bool nearb = (!f->seam && (x < m || x > (float)f->W - m)) || y < m || y > (float)f->H - m;
             if (status[i] && !polar && !nearb && (usable.empty() || usable[i])) good.push_back(i);
         }
         std::vector<uint8_t> inl(good.size(), 1);
@@ -1253,6 +1323,32 @@ int erp_frontend_set_equalize(erp_frontend* f, const erp_equalize_params* p) {
     const int rc = erp_equalize_check(p, f->W, f->H, f->W, f->W);
     if (rc) return rc;
     f->eq = *p;
+    return VIO_OK;
+}
+
+// ---- seam mode ----
+
+int erp_tracker_set_seam(erp_tracker* t, int seam) {
+    if (!t) return VIO_EINVAL;
+    if (seam != VIO_SEAM_CUT && seam != VIO_SEAM_WRAP) {
+        set_error(t->ctx, "erp_tracker_set_seam: unknown seam mode");
+        return VIO_EINVAL;
+    }
+    if (seam != t->seam && t->run_graph) {  // a captured run would replay the other mode's launches
+        (void)hipGraphExecDestroy(t->run_graph);
+        t->run_graph = nullptr;
+    }
+    t->seam = seam;
+    return VIO_OK;
+}
+
+int erp_frontend_set_seam(erp_frontend* f, int seam) {
+    if (!f) return VIO_EINVAL;
+    // the front end's LK parameters (frontend_track_slot1) and its min_distance
+    int rc = seam_mode_ok(f->t->ctx, seam, f->W, f->H, 21, 3, (double)f->p.min_distance, "erp_frontend_set_seam");
+    if (rc) return rc;
+    if ((rc = erp_tracker_set_seam(f->t, seam))) return rc;
+    f->seam = seam;
     return VIO_OK;
 }
 

@@ -8,10 +8,19 @@ namespace vio360 {
 
 constexpr int TRK_MAX_LEVELS = 8;
 
+// LK staging tiles (lk_kernel): the previous frame's patch tile and the next frame's region.  In seam wrap mode a
+// level must be at least LK_R wide (erp_seam_check): a tile then crosses the seam at most once
+constexpr int LK_WIN_MAX = 21;
+constexpr int LK_T = LK_WIN_MAX + 3;  // prev tile (patch + 1 bilinear + 1 Scharr each side)
+constexpr int LK_D = LK_WIN_MAX + 1;  // derivative / next tile
+constexpr int LK_MARGIN = 8;          // staged next-frame region: the window +- 8 px
+constexpr int LK_R = LK_D + 2 * LK_MARGIN;
+
 struct PyrLevelPair {  // one pyramid level of both frames (same geometry)
     uint8_t* p0;
     uint8_t* p1;
     int w, h, pitch;
+    int x_wrap;  // seam wrap mode: the edge columns continue periodically (w even) instead of REFLECT_101
 };
 
 struct LkLevel {
@@ -31,6 +40,7 @@ struct LkArgs {
     float min_eig;
     double eps2;
     float* bear1;  // [n][3] or null: the bearing of each tracked point (tracker pipeline: RANSAC's input)
+    int x_wrap;    // seam wrap mode: columns modulo the level width, no sideways exit, next.x folded into [0, W)
 };
 
 struct RansacArgs {
@@ -58,6 +68,7 @@ struct RansacArgs {
     float* rot;            // [iters][9] each hypothesis' rotation (ransac_hyp), read back for the best
     uint8_t* kept;         // [n] output mask in input order
     int* n_in;             // device scalar
+    int x_wrap;            // seam wrap mode (mode 1): no left / right margin, the mask look-up folds its column
 };
 
 struct GfArgs {
@@ -120,6 +131,9 @@ struct GfArgs {
     unsigned int* done;
     const unsigned int* wait_ctr;
     unsigned int wait_target;
+    // seam wrap mode (the map path only: eig map, masked maximum, candidates, greedy pass): columns continue
+    // periodically, no side margins, candidates at every x, the min-distance test on the cylinder
+    int x_wrap;
 };
 
 constexpr int LM_TX = 64, LM_TY = 32, LM_CAP = 1024;
@@ -143,6 +157,7 @@ struct DiscArgs {
     uint32_t* bits;
     int words, W, H, radius;
     const int* halfw;       // [radius+1]
+    int x_wrap;             // seam wrap mode: disc columns modulo W (radius < W / 2)
 };
 
 hipError_t launch_pyr_down(const PyrLevelPair& s, const PyrLevelPair& d, int frames, hipStream_t st);

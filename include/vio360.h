@@ -913,6 +913,46 @@ int erp_frontend_set_mask_device(erp_frontend* f, const uint8_t* dmask, int W, i
 int erp_frontend_set_mask_warped(erp_frontend* f, erp_warp* w, const uint8_t* src_mask, int stride,
                                  const erp_mask_params* p);
 
+/* Seam mode: an equirectangular frame is a cylinder, column W - 1 is adjacent to column 0.
+   VIO_SEAM_CUT (the default) is the reference's flat picture: REFLECT_101 columns, a point whose window leaves the
+   frame sideways is lost, boundary_margin columns are cut at the left and right, distances are flat.
+   VIO_SEAM_WRAP: every operation of the tracking path is the CUT operation applied to the horizontally periodic
+   continuation of the frame, and resulting x coordinates are folded into [0, W).  The y axis keeps every rule.
+     pyramids   the pyrDown border columns come from the opposite side of the level
+     LK         template, Scharr neighbours and next-frame window take columns modulo the level width; only the y
+                parts of the "left the frame" tests remain; the iteration runs in unwrapped coordinates and only the
+                final next.x is folded, by one f32 +-W (a fold that rounds to W gives 0; a point further than W
+                from the frame, or not a number, is lost: status 0)
+     filter     no left / right margin (top, bottom and polar stay); the region mask is read at the folded column
+     discs      CreateFeatureMask's disc columns are taken modulo W
+     GFTT       Sobel, 3x3 box and 3x3 NMS with wrapped neighbours; no left / right margin; candidates at every
+                x in [0, W), y in [1, H - 2]; threshold, sort and tie order unchanged; a candidate is rejected when
+                min(|dx|, W - |dx|)^2 + dy^2 < min_dist^2 against an accepted corner
+   The front end's grid assignment, RemoveClusteredFeatures and LimitFeaturesPerGrid stay flat (cells at the seam
+   are separate cells), and vio_ba_gather still drops observations within its boundary_margin of the left and right
+   edges.  Every frame entry (upload, resized, pixels, warped, equalised, masked) composes with the mode.
+   erp_seam_check (host only) is the check every WRAP call makes before it launches anything; VIO_EINVAL when
+     W is not divisible by 2^top, top = the pyramid level LK really uses for (W, H, win, max_level): only then is
+       a wrapped pyrDown the pyrDown of the continuation;
+     the top level is narrower than the LK staging tiles (38 columns);
+     W <= 2 min_dist (a disc or a min-distance neighbourhood would meet itself);
+   or when an argument is out of range.  erp_gftt_seam checks (W, H, 3, 0, min_dist). */
+enum { VIO_SEAM_CUT = 0, VIO_SEAM_WRAP = 1 };
+int erp_seam_check(int W, int H, int win, int max_level, double min_dist);
+/* erp_klt_track / erp_gftt with a seam mode; VIO_SEAM_CUT is erp_klt_track / erp_gftt bit for bit */
+int erp_klt_track_seam(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                       const float* pts, int n, float* next, uint8_t* status, float* err,
+                       const erp_klt_params* params, int seam);
+int erp_gftt_seam(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H, int stride,
+                  int max_corners, double quality, double min_dist, float* out_xy, int* n_out, int seam);
+/* the pipeline's mode, from the next erp_tracker_run on (which then makes the check with its own parameters and
+   returns VIO_EINVAL without a launch when it fails).  WRAP runs take the exact route through detection: the
+   eigenvalue map, its masked maximum and the candidate sort on the main stream. */
+int erp_tracker_set_seam(erp_tracker* t, int seam);
+/* the front end's mode, from the next frame on: LK, the boundary filter, the discs and detection follow it.  The
+   check is made here, with the front end's LK parameters (21 / 3) and min_distance. */
+int erp_frontend_set_seam(erp_frontend* f, int seam);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

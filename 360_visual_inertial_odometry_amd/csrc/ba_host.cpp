@@ -140,6 +140,7 @@ int analyze_window(vio_ctx* ctx, const vio_ba_problem& p, Packed& pk, std::vecto
     BaWin w;
     std::memset(&w, 0, sizeof w);
     w.K = K; w.L = L; w.N = N; w.variant = p.variant;
+    ba_win_set_geometry(w);
     w.is_vi = vi; w.is_pnp = pnp;
     w.max_iter = p.max_iterations;
     w.fixed_iter = p.fixed_iterations;
@@ -380,7 +381,7 @@ static int pack_upload(vio_ctx* ctx, BaDevice& d, const vio_ba_problem* probs, i
     const int cm = cmax > 0 ? cmax : ctx->ba_route == VIO_BA_ROUTE_CLUSTER ? (1 << 20) : 0;
     d.cluster_C = allow_cluster && cluster_wanted(ctx, n) ? ba_cluster_members(pk.win.data(), n, cm) : 0;
     const int gs = schur_group_size(n, d.cluster_C > 0);
-    for (BaWin& w : pk.win) w.gs = gs;
+    for (BaWin& w : pk.win) ba_win_set_gs(w, gs);
     layout_regions(pk, n, d.cluster_C > 0);
     const BaRegions& R = pk.R;
     uint8_t* dev = nullptr;
@@ -686,7 +687,7 @@ static int batch_fall_back(vio_ctx* ctx, BaDevice& d) {
     d.cluster_C = 0;
     d.P.csync = nullptr;
     const int gs = schur_group_size(d.n, false);
-    for (BaWin& w : d.pk.win) w.gs = gs;
+    for (BaWin& w : d.pk.win) ba_win_set_gs(w, gs);
     std::memcpy(d.stage + d.pk.R.win, d.pk.win.data(), sizeof(BaWin) * (size_t)d.n);
     VIO_DEVICE(ctx);
     VIO_HIP(ctx, hipMemcpyAsync((void*)d.P.win, d.stage + d.pk.R.win, sizeof(BaWin) * (size_t)d.n,
@@ -747,6 +748,23 @@ int vio_layout_check(void) {
                    gba == gba_layout_sig_ba_kernel() && gba == gba_layout_sig_ba_global_host()
                ? VIO_OK
                : VIO_EDEVICE;
+}
+
+int vio_ba_walk_geometry(int num_kf, int num_lm, int group_size, int32_t out[5]) {
+    if (num_kf < 0 || num_kf > BA_KMAX || num_lm < 0 || group_size < 1 || !out) return VIO_EINVAL;
+    BaWin w;
+    std::memset(&w, 0, sizeof w);
+    w.K = num_kf;
+    w.L = num_lm;
+    ba_win_set_geometry(w);
+    ba_win_set_gs(w, group_size);
+    out[0] = w.LC; out[1] = w.nch; out[2] = w.ng; out[3] = w.rK; out[4] = w.rLC;
+    return VIO_OK;
+}
+
+int vio_ba_walk_div(int t, int recip) {
+    if (t < 0 || t >= WALK_TMAX || recip < 1 || recip > (1 << WALK_SHIFT)) return VIO_EINVAL;
+    return walk_div(t, recip);
 }
 
 int vio_ctx_create(int device, vio_ctx** out) {

@@ -575,16 +575,20 @@ __device__ __forceinline__ void jac_from_ap(const double* A, const double* Pb, c
 // the landmark-sorted SoA arrays, so consecutive lanes touch consecutive observations (coalesced),
 // a lane keeps one keyframe (its pose cache / pose sums) for the whole walk, and landmark sums are
 // fixed-order reductions over the K lanes of a slot through LDS.
+// No division by a per-window value: LC and the reciprocals of K and LC come with the window descriptor
+// (BaWin::LC / rK / rLC, walk_div of ba_types.h).
 struct Walk {
     int LC, jf, kf;
+    int rLC;  // walk_recip(LC): the landmark sums' t / LC
     bool on;
 };
-__device__ __forceinline__ Walk walk_geom(int K) {
+__device__ __forceinline__ Walk walk_geom(const BaWin& w) {
     Walk g;
-    const int k = K > 0 ? K : 1;
-    g.LC = BA_THREADS / k;
-    g.jf = threadIdx.x / k;
-    g.kf = threadIdx.x - g.jf * k;
+    const int K = w.K, k = K > 0 ? K : 1;
+    g.LC = w.LC;
+    g.rLC = w.rLC;
+    g.jf = walk_div((int)threadIdx.x, w.rK);
+    g.kf = (int)threadIdx.x - g.jf * k;
     g.on = K > 0 && g.jf < g.LC;
     return g;
 }
@@ -598,7 +602,7 @@ __device__ __forceinline__ double lm_sums9(const double* q, int l0, const Walk& 
                                            const uint8_t* lm_var, const double* xl, double* V, double* gl, double* sl,
                                            bool first, double gm) {
     for (int t = threadIdx.x; t < 9 * g.LC; t += BA_THREADS) {
-        const int i = t / g.LC, j = t - i * g.LC, lj = l0 + j;
+        const int i = walk_div(t, g.rLC), j = t - i * g.LC, lj = l0 + j;
         if (lj >= L || !lm_var[lj]) continue;
         const double* src = q + i * BA_THREADS + j * K;
         double v = 0.0;
@@ -662,7 +666,7 @@ __device__ __forceinline__ double eval_lin(BaShared& sh, const WinCtx& c, const 
     __syncthreads();
     // R_bw at this linearisation point for the Schur / back-substitution walks (later barriers order it)
     for (int e = threadIdx.x; e < 9 * K; e += BA_THREADS) sh.Rlin[e / 9][e % 9] = sh.pc[e / 9][12 + e % 9];
-    const Walk g = walk_geom(K);
+    const Walk g = walk_geom(w);
     const int pf = g.on ? sh.posef[g.kf] : -1;
     const int* lk = reinterpret_cast<const int*>(c.ws + c.L.lk);
     double* r0 = c.ws + c.L.r;
@@ -1518,7 +1522,7 @@ __device__ __forceinline__ void compute_step(BaShared& sh, const WinCtx& c) {
     __syncthreads();
     pose_cache(sh, c, cp_);  // sh.pc now holds the candidate poses (the step uses sh.Rlin)
     __syncthreads();
-    const Walk g = walk_geom(K);
+    const Walk g = walk_geom(w);
     const int pf = g.on ? sh.posef[g.kf] : -1;
     const int* lk = reinterpret_cast<const int*>(c.ws + c.L.lk);
     const double* r0 = c.ws + c.L.r;

@@ -148,12 +148,13 @@ struct PhLayout {
     int LC, nch, ng;
 };
 // phase region of a window (doubles, after ba_ws_layout().total + ba_ws_extra_doubles())
-__host__ __device__ inline PhLayout ph_layout(int K, int L, int N, int T, int gs) {
+// (LC, nch, ng: the walk geometry, which the kernels take from the window descriptor instead of dividing)
+__host__ __device__ inline PhLayout ph_layout_at(int K, int L, int N, int T, int LC, int nch, int ng) {
     PhLayout p;
     const int k = K > 0 ? K : 1;
-    p.LC = BA_THREADS / k;
-    p.nch = (L + p.LC - 1) / p.LC;
-    p.ng = (p.nch + gs - 1) / gs;
+    p.LC = LC;
+    p.nch = nch;
+    p.ng = ng;
     const int nt = T * (T + 1) / 2;
     int64_t o = 0;
     p.st = o; o += 64;
@@ -185,6 +186,13 @@ __host__ __device__ inline PhLayout ph_layout(int K, int L, int N, int T, int gs
     p.himu2 = o; o += NI_MAX * NI_MAX + NI_MAX;      // IMU normal equations (H, g) of the second set
     p.total = (o + 31) & ~(int64_t)31;
     return p;
+}
+__host__ __device__ inline PhLayout ph_layout(int K, int L, int N, int T, int gs) {
+    const int LC = BA_THREADS / (K > 0 ? K : 1), nch = (L + LC - 1) / LC;
+    return ph_layout_at(K, L, N, T, LC, nch, (nch + gs - 1) / gs);
+}
+__host__ __device__ inline PhLayout ph_layout(const BaWin& w) {
+    return ph_layout_at(w.K, w.L, w.N, w.T, w.LC, w.nch, w.ng);
 }
 
 static_assert(1500 + 3 * BA_THREADS <= 9 * BA_THREADS && 8 + NI_MAX * NI_MAX + NI_MAX + (BA_KMAX * NI_MAX) / 8 <= 1500,
@@ -236,6 +244,7 @@ __device__ inline int ph_wy(const BaPools& P) { return P.win_base + (int)blockId
 // the kernel's dynamic LDS (ph_cluster_lds_bytes)
 struct PhClusterSh;
 __device__ __forceinline__ PhState* ph_lds_state();
+__device__ __forceinline__ void ph_ctx_view(PhCtx& x, bool sw);
 
 // LS: the window's PhState lives in LDS (the cluster route's leader keeps its LM state on chip for the whole
 // solve, ph_cluster_kernel); otherwise in the window's phase region
@@ -266,10 +275,22 @@ __device__ __forceinline__ PhCtx ph_ctx(const BaPools& P, int wi, int cur_overri
     c.gimu = c.Himu + NI_MAX * NI_MAX;
     c.outlier = P.out_u8 + w.o_obs;
     c.trace = P.out_trace + w.o_tr;
-    x.ph = ph_layout(w.K, w.L, w.N, w.T, w.gs);
+    x.ph = ph_layout(w);
     x.pr = c.ws + c.L.total + ba_ws_extra();
     x.gs = LS ? ph_lds_state() : reinterpret_cast<PhState*>(x.pr + x.ph.st);
-    const bool sw = (cur_override >= 0 ? cur_override : x.gs->cur) != 0;
+    ph_ctx_view(x, (cur_override >= 0 ? cur_override : x.gs->cur) != 0);
+    return x;
+}
+// the same window's context with parameter set `cur` as the current point (only the view differs: a kernel
+// that has built one context derives the other from it instead of building it again)
+__device__ __forceinline__ PhCtx ph_ctx_at(const PhCtx& x0, int cur) {
+    PhCtx x = x0;
+    ph_ctx_view(x, cur != 0);
+    return x;
+}
+// sw: parameter / linearisation set 1 is the current point, set 0 the candidate
+__device__ __forceinline__ void ph_ctx_view(PhCtx& x, bool sw) {
+    const WinCtx& c = x.c;
     double* s0[4] = {c.ws + c.L.x_pose, c.ws + c.L.x_lm, c.ws + c.L.x_vel, c.ws + c.L.x_bias};
     double* s1[4] = {c.ws + c.L.c_pose, c.ws + c.L.c_lm, c.ws + c.L.c_vel, c.ws + c.L.c_bias};
     double** X = sw ? s1 : s0;
@@ -282,15 +303,12 @@ __device__ __forceinline__ PhCtx ph_ctx(const BaPools& P, int wi, int cur_overri
     x.imurc = x.pr + (sw ? x.ph.imur : x.ph.imurc);
     x.himu = sw ? x.pr + x.ph.himu2 : c.Himu;
     x.himuc = sw ? c.Himu : x.pr + x.ph.himu2;
-    const int64_t N = w.N;
-    (void)N;
     double* l0[6] = {c.ws + c.L.r, c.ws + c.L.jp, c.ws + c.L.V, c.ws + c.L.gl, x.pr + x.ph.upart, x.pr + x.ph.lpart};
     double* l1[6] = {x.pr + x.ph.r2, x.pr + x.ph.a2, x.pr + x.ph.v2, x.pr + x.ph.gl2, x.pr + x.ph.upart2, x.pr + x.ph.lpart2};
     double** LC_ = sw ? l1 : l0;
     double** LN_ = sw ? l0 : l1;
     x.lr = LC_[0]; x.la = LC_[1]; x.lv = LC_[2]; x.lg = LC_[3]; x.lup = LC_[4]; x.llp = LC_[5];
     x.cr = LN_[0]; x.ca = LN_[1]; x.cvv = LN_[2]; x.cgl = LN_[3]; x.cup = LN_[4]; x.clp = LN_[5];
-    return x;
 }
 
 // keyframe tables of a window into LDS
@@ -479,7 +497,7 @@ __device__ __forceinline__ void ph_lin_body(const BaPools& P, int wi, int ci, Ph
     ph_tables(sh, x);
     ph_pose_cache(sh, x, xp);
     __syncthreads();
-    const Walk g = walk_geom(K);
+    const Walk g = walk_geom(w);
     const int pf = g.on ? sh.posef[g.kf] : -1;
     const int* lk = reinterpret_cast<const int*>(ws + c.L.lk);
     double* r0 = x.lr;
@@ -559,7 +577,7 @@ __device__ __forceinline__ void ph_lin_body(const BaPools& P, int wi, int ci, Ph
         for (int i = 0; i < 9; ++i) sh.buf[i * BA_THREADS + threadIdx.x] = acc[9 * part + i];
         __syncthreads();
         for (int e = threadIdx.x; e < 9 * K; e += BA_THREADS) {
-            const int k = e / 9, i = e - 9 * k;
+            const int k = walk_div(e, walk_recip(9)), i = e - 9 * k;  // (e < 9 K <= 144: exact, full-rate multiply)
             double s = 0.0;
             for (int j = 0; j < g.LC; ++j) s += sh.buf[i * BA_THREADS + j * K + k];
             st_w<WT>(up + 27 * k + 9 * part + i, s);
@@ -1851,14 +1869,14 @@ struct WalkLane {
 // the lane inputs of chunk ci (o, landmark lanes) from memory (no tables needed); o_pre >= -1: the lane's
 // observation index already read (ph_back_launch requests it with the window state: the landmark-keyframe
 // table does not depend on the parameter set)
-__device__ __forceinline__ void ph_walk_lm_inputs(const PhCtx& x, int ci, WalkLane& wl);
+__device__ __forceinline__ void ph_walk_lm_inputs(const PhCtx& x, const Walk& g, int ci, WalkLane& wl);
 // (lm_now false: the landmark lanes' step inputs are left for ph_walk_lm_inputs, called just before the step)
-__device__ __forceinline__ void ph_walk_inputs(const PhCtx& x, int ci, WalkLane& wl, double (&pw)[3], double& a_o,
-                                               int o_pre = -2, bool lm_now = true) {
+// (g: the window's walk geometry, formed once per workgroup by the caller -- walk_geom reads the descriptor)
+__device__ __forceinline__ void ph_walk_inputs(const PhCtx& x, const Walk& g, int ci, WalkLane& wl, double (&pw)[3],
+                                               double& a_o, int o_pre = -2, bool lm_now = true) {
     const WinCtx& c = x.c;
     const BaWin& w = *c.w;
     const int N = w.N, K = w.K, L = w.L;
-    const Walk g = walk_geom(K);
     const int l0 = ci * g.LC, l = l0 + g.jf;
     wl.o = o_pre >= -1 ? o_pre : (g.on && l < L) ? reinterpret_cast<const int*>(c.ws + c.L.lk)[16 * l + g.kf] : -1;
     wl.lv = wl.out_o = false;
@@ -1877,15 +1895,14 @@ __device__ __forceinline__ void ph_walk_inputs(const PhCtx& x, int ci, WalkLane&
         wl.vo = (double)c.obs_uv[2 * o + 1];
         wl.out_o = c.outlier[o] != 0;
     }
-    if (lm_now) ph_walk_lm_inputs(x, ci, wl);
+    if (lm_now) ph_walk_lm_inputs(x, g, ci, wl);
 }
 // the landmark lanes' inputs of the landmark step (lane j < LC: landmark l0 + j): Jacobi scale, gradient,
 // V~^-1 factor, position
-__device__ __forceinline__ void ph_walk_lm_inputs(const PhCtx& x, int ci, WalkLane& wl) {
+__device__ __forceinline__ void ph_walk_lm_inputs(const PhCtx& x, const Walk& g, int ci, WalkLane& wl) {
     const WinCtx& c = x.c;
     const BaWin& w = *c.w;
     const int L = w.L;
-    const Walk g = walk_geom(w.K);
     const int l0 = ci * g.LC;
     const int lj = l0 + (int)threadIdx.x;
     wl.lane_lm = (int)threadIdx.x < g.LC && lj < L;
@@ -1909,9 +1926,8 @@ __device__ __forceinline__ void ph_walk_lm_inputs(const PhCtx& x, int ci, WalkLa
     }
 }
 // the observation's Jacobian at the linearisation point (sh.Rlin, sh.Rcb_raw in LDS)
-__device__ __forceinline__ void ph_walk_jac(const PhShared& sh, const BaWin& w, WalkLane& wl, const double (&pw)[3],
-                                            double a_o) {
-    const Walk g = walk_geom(w.K);
+__device__ __forceinline__ void ph_walk_jac(const PhShared& sh, const BaWin& w, const Walk& g, WalkLane& wl,
+                                            const double (&pw)[3], double a_o) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) wl.J.j6[i] = 0.0;
 #pragma unroll
@@ -1930,11 +1946,12 @@ __device__ __forceinline__ void ph_back_pre(const BaPools& P, PhShared& sh, int 
     const PhCtx x = ph_ctx(P, wi, cur);
     double pw[3], a_o;
     WalkLane wl;
-    ph_walk_inputs(x, ci, wl, pw, a_o);
+    const Walk g = walk_geom(*x.c.w);
+    ph_walk_inputs(x, g, ci, wl, pw, a_o);
     ph_tables(sh, x);
     ph_ld_block(&sh.Rlin[0][0], x.pr + x.ph.rlin, PL24 * x.c.w->K);
     __syncthreads();
-    ph_walk_jac(sh, *x.c.w, wl, pw, a_o);
+    ph_walk_jac(sh, *x.c.w, g, wl, pw, a_o);
 #pragma unroll
     for (int i = 0; i < 12; ++i) jl[i * BA_THREADS + threadIdx.x] = wl.J.p12[i];
 #pragma unroll
@@ -1955,11 +1972,11 @@ __host__ __device__ constexpr int ph_pair_b(int q) {
 static_assert(ph_pair_a(0) == 0 && ph_pair_b(5) == 5 && ph_pair_a(6) == 1 && ph_pair_b(6) == 1 && ph_pair_a(20) == 5 &&
                   ph_pair_b(20) == 5, "pair order");
 // jl (non-null): the lanes' Jacobians from the prelude (ph_back_pre; the tables and sh.Rlin are in LDS too)
+// (x, g: the window's context at parameter set v.cur and its walk geometry, built once per workgroup)
 template <bool EXTRA, bool WT = true>
-__device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int wi, int ci, const PhView& v,
-                                             const double* jl = nullptr, int o_pre = -2) {
+__device__ __forceinline__ void ph_back_body_at(const BaPools& P, PhShared& sh, const PhCtx& x, const Walk& g, int wi,
+                                                int ci, const PhView& v, const double* jl = nullptr, int o_pre = -2) {
     const bool pre = jl != nullptr;
-    const PhCtx x = ph_ctx(P, wi, v.cur);
     const WinCtx& c = x.c;
     const BaWin& w = *c.w;
     if (ci > x.ph.nch || (!EXTRA && ci == x.ph.nch)) return;
@@ -1967,13 +1984,12 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
     const unsigned long long wstart = P.prof ? __builtin_amdgcn_s_memtime() : 0;
     // the lane's observation and its linearisation inputs, requested before the window tables (one memory
     // round trip for both instead of two in sequence) -- or the cluster member's prelude (ph_back_pre)
-    const Walk g = walk_geom(K);
     const int l0 = ci * g.LC;
     WalkLane wl;
     double pw[3], a_o;
     // (with the prelude: the same loads again, its Jacobian kept; phase route: the landmark lanes' inputs
     // requested after the Jacobian, so that they are not live across it -- no spill at five waves per SIMD)
-    ph_walk_inputs(x, ci, wl, pw, a_o, o_pre, WT);
+    ph_walk_inputs(x, g, ci, wl, pw, a_o, o_pre, WT);
     const int o = wl.o, lj = l0 + (int)threadIdx.x;
     const bool lv = wl.lv, out_o = wl.out_o;
     const double uo = wl.uo, vo = wl.vo;
@@ -2023,7 +2039,7 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
 #pragma unroll
         for (int i = 0; i < 6; ++i) wl.J.j6[i] = jl[(12 + i) * BA_THREADS + threadIdx.x];
     } else {
-        ph_walk_jac(sh, w, wl, pw, a_o);
+        ph_walk_jac(sh, w, g, wl, pw, a_o);
     }
     const double* p12 = wl.J.p12;
     const double* j6 = wl.J.j6;
@@ -2040,7 +2056,7 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
         }
     }
     const bool contrib = lv && pf >= 0;
-    if (!WT) ph_walk_lm_inputs(x, ci, wl);
+    if (!WT) ph_walk_lm_inputs(x, g, ci, wl);
     const bool lane_lm = wl.lane_lm, lvj = wl.lvj;
     const double* sv = wl.sv;
     const double* glj = wl.glj;
@@ -2101,6 +2117,11 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
     // (the 27 pose-partial terms are formed per pass from jpk / rsk below: 14 live values instead of 27 across
     // the landmark sums, 121 -> 110 VGPRs; the same expressions, contracted into FMAs in another order, so
     // the partials can differ in the last bit from the round-5 build)
+    // (the lane's model change waits in LDS across the candidate evaluation, not in two of ph_back_kernel's 96
+    // registers: red's slots are free from the barrier above to the one below; the compiler barrier before the
+    // reload keeps it from forwarding the value in a register all the same)
+    double* mcs = red;
+    mcs[threadIdx.x] = 0.0;
     double jpk[12], rsk[2] = {0.0, 0.0}, v9[9];
 #pragma unroll
     for (int i = 0; i < 12; ++i) jpk[i] = 0.0;
@@ -2117,6 +2138,7 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
             }
         }
         mc -= m0 * (ra + m0 / 2.0) + m1 * (rb + m1 / 2.0);
+        mcs[threadIdx.x] = mc;
         double Pc[3] = {cps[3 * g.jf], cps[3 * g.jf + 1], cps[3 * g.jf + 2]};
         double r[2], Pcam[3], Lc = 0.0, iLc = 0.0;
         bool tail;
@@ -2163,6 +2185,8 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
             }
         }
     }
+    asm volatile("" ::: "memory");
+    mc = mcs[threadIdx.x];
     __syncthreads();  // buf (red / dls / cps) is reused below
     // landmark sums of the candidate linearisation (the chunk's landmarks), gradient terms at the
     // candidate points (cl, written above by this workgroup's landmark lanes)
@@ -2183,7 +2207,7 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
         });
         __syncthreads();
         for (int e = threadIdx.x; e < 9 * K; e += BA_THREADS) {
-            const int k = e / 9, i = e - 9 * k;
+            const int k = walk_div(e, walk_recip(9)), i = e - 9 * k;  // (e < 9 K <= 144: exact, full-rate multiply)
             double s = 0.0;
             for (int j = 0; j < g.LC; ++j) s += sh.buf[i * BA_THREADS + j * K + k];
             st_w<WT>(up + 27 * k + 9 * part + i, s);
@@ -2208,6 +2232,13 @@ __device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int
     }
 }
 
+template <bool EXTRA, bool WT = true>
+__device__ __forceinline__ void ph_back_body(const BaPools& P, PhShared& sh, int wi, int ci, const PhView& v,
+                                             const double* jl = nullptr, int o_pre = -2) {
+    const PhCtx x = ph_ctx(P, wi, v.cur);
+    ph_back_body_at<EXTRA, WT>(P, sh, x, walk_geom(*x.c.w), wi, ci, v, jl, o_pre);
+}
+
 template <bool EXTRA>
 __device__ __forceinline__ void ph_back_launch(const BaPools& P, PhShared& sh) {
     const int wi = ph_wy(P);
@@ -2216,14 +2247,15 @@ __device__ __forceinline__ void ph_back_launch(const BaPools& P, PhShared& sh) {
     // the lane's observation index, requested with the window state (one round trip for both; the walk's
     // other inputs depend on the current parameter set, i.e. on the state)
     const BaWin& w0 = *x0.c.w;
-    const Walk g0 = walk_geom(w0.K);
+    const Walk g0 = walk_geom(w0);
     const int ci = (int)blockIdx.x, l = ci * g0.LC + g0.jf;
     const int o_pre = (g0.on && ci < x0.ph.nch && l < w0.L)
                           ? reinterpret_cast<const int*>(x0.c.ws + x0.c.L.lk)[16 * l + g0.kf] : -1;
     const PhState& gst = *x0.gs;
     if (gst.st.done || !gst.step_valid) return;
     PhView v{gst.cur, 0, 1, 0.0, nullptr};
-    ph_back_body<EXTRA, false>(P, sh, wi, ci, v, nullptr, o_pre);
+    // one context per workgroup: the view at the current parameter set from the one built above
+    ph_back_body_at<EXTRA, false>(P, sh, ph_ctx_at(x0, gst.cur), g0, wi, ci, v, nullptr, o_pre);
 }
 #ifndef VIO_BA_CLUSTER_TU
 __global__ void __launch_bounds__(BA_THREADS, 4) ph_back_kernel(BaPools P) {

@@ -30,6 +30,10 @@ struct BaWin {
     int32_t pose_f[BA_KMAX];     // f-offset of pose k or -1 (constant / unused)
     int32_t vel_f[BA_KMAX];      // f-offset of velocity k or -1
     int32_t bg_f, ba_f;
+    // walk geometry, fixed per window (ba_win_set_geometry / ba_win_set_gs): landmarks per chunk
+    // BA_THREADS / max(K, 1), chunks ceil(L / LC), Schur groups ceil(nch / gs), and the multiply-shift
+    // reciprocals of K and LC (walk_recip) so that no kernel divides by a per-window value
+    int32_t LC, nch, ng, rK, rLC;
     double cols, rows, huber, chi2_thr;
     double Lw[4], info[4];
     double gravity[3], bg0[3], ba0[3], _p1;
@@ -80,8 +84,9 @@ struct BaPools {
 };
 // BaWin / BaPools cross translation units (ba_host.cpp packs them, ba_kernel.hip reads them): pinned
 // here in every TU that includes this header, and cross-checked at run time (ba_layout_sig).
-static_assert(sizeof(BaWin) == 448 && offsetof(BaWin, gravity) == 304 && offsetof(BaWin, o_ws) == 424 &&
-              offsetof(BaWin, o_tr) == 440, "BaWin layout changed: update the pinned offsets");
+static_assert(sizeof(BaWin) == 464 && offsetof(BaWin, LC) == 204 && offsetof(BaWin, gravity) == 320 &&
+              offsetof(BaWin, o_ws) == 440 && offsetof(BaWin, o_tr) == 456,
+              "BaWin layout changed: update the pinned offsets");
 static_assert(sizeof(BaPools) == 216 && offsetof(BaPools, prof) == 184 && offsetof(BaPools, route) == 192 &&
               offsetof(BaPools, imu_in_back) == 200 && offsetof(BaPools, chol_variant) == 204 &&
               offsetof(BaPools, csync) == 208,
@@ -98,6 +103,38 @@ uint64_t ba_layout_sig_ba_global_host();
 uint64_t gba_layout_sig_ba_kernel();
 uint64_t gba_layout_sig_ba_global_host();
 uint64_t gba_layout_sig_ba_global();
+
+// Division-free walk geometry.  t / d for a per-window divisor d (K or LC, 1 <= d <= BA_THREADS) is
+// (t * walk_recip(d)) >> WALK_SHIFT, exact for 0 <= t < WALK_TMAX: with r = ceil(2^20 / d) the error
+// e = r d - 2^20 is in [0, d), and the quotient is exact while t e < 2^20, which 4096 * 255 < 2^20
+// guarantees; t r < 2^12 * 2^20 fits 32 bits.  The walks' arguments are a thread index (< BA_THREADS)
+// and the 9 x LC landmark-sum jobs (< 9 * BA_THREADS = 2304).  tests/test_walk_geometry.py checks every
+// argument of every K against integer division through vio_ba_walk_geometry / vio_ba_walk_div.
+constexpr int WALK_SHIFT = 20;
+constexpr int WALK_TMAX = 4096;
+static_assert(9 * BA_THREADS <= WALK_TMAX && (int64_t)WALK_TMAX * (BA_THREADS - 1) < (int64_t)1 << WALK_SHIFT,
+              "walk_div is exact over the walks' argument range");
+__host__ __device__ constexpr int32_t walk_recip(int d) { return (int32_t)((((uint32_t)1 << WALK_SHIFT) + d - 1) / d); }
+__host__ __device__ inline int walk_div(int t, int32_t r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)(__umul24((unsigned)t, (unsigned)r) >> WALK_SHIFT);  // both below 2^24: the full-rate multiply
+#else
+    return (int)(((uint32_t)t * (uint32_t)r) >> WALK_SHIFT);
+#endif
+}
+// the geometry fields of a window descriptor from its K and L (pack time)
+inline void ba_win_set_geometry(BaWin& w) {
+    const int k = w.K > 0 ? w.K : 1;
+    w.LC = BA_THREADS / k;
+    w.nch = (w.L + w.LC - 1) / w.LC;
+    w.rK = walk_recip(k);
+    w.rLC = walk_recip(w.LC);
+}
+// the Schur group size of a window (per batch, at upload) and the group count that follows from it
+inline void ba_win_set_gs(BaWin& w, int gs) {
+    w.gs = gs;
+    w.ng = (w.nch + gs - 1) / gs;
+}
 
 // workspace sub-offsets (in doubles) relative to BaWin::o_ws
 struct BaWsLayout {

@@ -61,6 +61,13 @@ int vio_abi_version(void);
  * internal cross-TU argument structs (a stale object after a header change is reported as VIO_EDEVICE
  * here and by vio_ctx_create instead of faulting a kernel); needs no GPU */
 int vio_layout_check(void);
+/* The division-free lane geometry of the window-BA walk kernels, as the packer writes it into a window's
+ * descriptor (needs no GPU; for tests): out = { LC = 256 / max(num_kf, 1) landmarks per chunk,
+ * ceil(num_lm / LC) chunks, ceil(chunks / group_size) Schur groups, the reciprocal of max(num_kf, 1), the
+ * reciprocal of LC }.  vio_ba_walk_div(t, recip) is the kernels' t / d for 0 <= t < 4096 given d's reciprocal
+ * (VIO_EINVAL outside that range). */
+int vio_ba_walk_geometry(int num_kf, int num_lm, int group_size, int32_t out[5]);
+int vio_ba_walk_div(int t, int recip);
 
 /* Window-BA execution route of this context's later solves / batches (the routes give the same
    results to roundoff, each with its own fixed summation order; within a route results do not depend

@@ -1,6 +1,6 @@
 // mask_host.cpp — host side of the region masks (erp_mask_*, include/vio360.h): the argument check, the per-axis
 // footprints of the conservative reduce (the taps of erp_resize_area_tab, what the frame's INTER_AREA resize reads)
-// and the launches of mask.hip's kernels.  The tracker's and the front end's entry points are in tracker_host.cpp.
+// and the launches of mask.hip's kernels.  The tracker's entry points are in tracker_host.cpp, the front end's forwards in frontend_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -265,6 +265,12 @@ __device__ void ransac_raw_body(uint32_t seed, uint32_t* raw, uint32_t* mt);  //
 __device__ float ransac_cos_bound(float thr);
 __device__ void pixel_to_bearing(float u, float v, int W, int H, float* b);
 constexpr int LK_AUX_BLOCKS = 17;  // LkAux: one workgroup for the raw draws, 16 for the reset and the bitmap clear
+// per-run reset of the GFTT scalars (one thread of gftt_reset_kernel, or of lk_aux in the pipeline)
+__device__ __forceinline__ void gftt_reset_scalars(int* scal) {
+    scal[TS_MAX_ORD] = scal[TS_N_CAND] = scal[TS_N_OUT] = 0;
+    scal[TS_N_TOP] = scal[TS_CUT] = scal[TS_CUT + 1] = scal[TS_INCOMPLETE] = 0;
+    scal[TS_LMAX_OVER] = scal[TS_N_FLAT] = 0;
+}
 __device__ void lk_aux(const LkAux& X, int b) {
     if (b == 0) {
         __shared__ uint32_t mt[624];
@@ -274,11 +280,7 @@ __device__ void lk_aux(const LkAux& X, int b) {
     }
     const size_t t = (size_t)(b - 1) * LK_THREADS + threadIdx.x, stride = (size_t)(LK_AUX_BLOCKS - 1) * LK_THREADS;
     if (X.hist) {  // gftt_reset_kernel's work
-        if (t == 0) {
-            X.scal[2] = X.scal[3] = X.scal[4] = 0;
-            X.scal[6] = X.scal[7] = X.scal[8] = X.scal[9] = 0;
-            X.scal[10] = X.scal[11] = 0;
-        }
+        if (t == 0) gftt_reset_scalars(X.scal);
         for (size_t i = t; i < (size_t)GF_BUCKETS; i += stride) X.hist[i] = 0u;
         for (size_t i = t; i < X.topk_cap; i += stride) X.topk[i] = 0ull;
     }
@@ -1791,11 +1793,7 @@ __global__ void __launch_bounds__(256) gftt_topk_compact_kernel(GfArgs G) {
 // per-frame reset of the GFTT counters, histogram and top-K buffer (one launch instead of memsets)
 __global__ void __launch_bounds__(256) gftt_reset_kernel(GfArgs G, int* scal) {
     const unsigned int t = blockIdx.x * 256 + threadIdx.x, stride = gridDim.x * 256;
-    if (t == 0) {
-        scal[2] = scal[3] = scal[4] = 0;             // max_ord, n_cand, n_out
-        scal[6] = scal[7] = scal[8] = scal[9] = 0;   // n_top, cut[2], incomplete
-        scal[10] = scal[11] = 0;                     // lmax overflow, flatten counter
-    }
+    if (t == 0) gftt_reset_scalars(scal);
     for (unsigned int i = t; i < GF_BUCKETS; i += stride) G.hist[i] = 0u;
     for (unsigned int i = t; i < G.topk_cap; i += stride) G.topk[i] = 0ull;
 }

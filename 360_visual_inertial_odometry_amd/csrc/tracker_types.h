@@ -1,5 +1,5 @@
 // tracker_types.h — kernel argument blocks of the ERP tracker (tracker.hip), shared with the host
-// side (tracker_host.cpp).
+// side (tracker_host.cpp, frontend_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -139,8 +139,34 @@ struct GfArgs {
 constexpr int LM_TX = 64, LM_TY = 32, LM_CAP = 1024;
 
 constexpr int GF_BUCKETS = 2048;    // float bits >> 20 of a positive response
-constexpr int kPresortWords = GF_BUCKETS + 8;  // the presort's histogram + scalars
-constexpr int kPresortClear = GF_BUCKETS + 6;  // cleared per run (word 6: the monotonic hand-off counter)
+
+// word index of every device scalar of a tracker (erp_tracker::d_scal, TS_COUNT ints)
+enum TrkScal {
+    TS_N_GOOD = 0,      // RANSAC: points that passed the input filter
+    TS_N_IN = 1,        // RANSAC: inliers of the best hypothesis
+    TS_MAX_ORD = 2,     // GFTT: ordered-int maximum of the masked eigenvalue map
+    TS_N_CAND = 3,
+    TS_N_OUT = 4,
+    TS_N_TOP = 6,
+    TS_CUT = 7,         // two words: [0] cut bucket [1] everything selected
+    TS_INCOMPLETE = 9,
+    TS_LMAX_OVER = 10,  // a tile held more local maxima than its slots
+    TS_N_FLAT = 11,     // fill counter of the flattened candidate list
+    TS_CMIN = 12,       // f32: the RANSAC inlier test's cosine bound
+    TS_COUNT = 16
+};
+// the presort's scalars (pipeline, side stream), word index after its histogram [GF_BUCKETS] in erp_tracker::d_hist2
+enum PresortScal {
+    PS_N_TOP = 0,
+    PS_CUT = 1,       // two words
+    PS_MAX_ORD = 3,   // stays zero: every key passes the presort's threshold test
+    PS_N_CAND = 4,
+    PS_SMAX = 5,      // maximum of the tiles' static-region maxima
+    PS_DONE = 6,      // the monotonic hand-off counter: not cleared per run
+    PS_COUNT = 8
+};
+constexpr int kPresortWords = GF_BUCKETS + PS_COUNT;  // the presort's histogram + scalars
+constexpr int kPresortClear = GF_BUCKETS + PS_DONE;   // cleared per run by gftt_lmax_kernel (GfArgs::clear)
 // top-K buffer: the strongest candidates (>= 16 x max_corners of them when the buckets allow) sorted
 // for the greedy selection; a selection that runs dry falls back to the full candidate sort
 constexpr unsigned int GF_TOPK_CAP = 16384;

@@ -43,9 +43,10 @@ def built(vio):
     ("ba_types.h", {"ba_kernel", "ba_host", "ba_global_host"}),
     ("ba_global.h", {"ba_kernel", "ba_global", "ba_global_host"}),
     ("chol_dev.h", {"ba_kernel", "ba_global"}),
-    ("vio360.h", {"ba_kernel", "ba_host", "ba_global", "ba_global_host", "tracker_host"}),
+    ("vio360.h", {"ba_kernel", "ba_host", "ba_global", "ba_global_host", "tracker_host", "frontend_host"}),
     ("resize.h", {"resize", "resize_host"}),
     ("frame_io.h", {"resize_host", "warp_host", "equalize_host", "mask_host", "tracker_host"}),
+    ("tracker_types.h", {"tracker", "tracker_host", "frontend_host"}),
 ])
 def test_touching_a_header_rebuilds_its_dependents(built, header, must):
     deps = set(_includers(header))

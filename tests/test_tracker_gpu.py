@@ -209,6 +209,108 @@ def test_pipeline_presel_cases_bitwise(vio, gpu_ctx, pair, npts, max_corners, qu
     assert fb == (tail, 0)
 
 
+PRESEL_CASES = [(300, 1000, 0.01), (300, 300, 0.3), (300, 4, 0.01), (100, 20, 0.01), (40, 4, 0.01)]
+
+
+def test_download_is_idempotent(vio, gpu_ctx, pair):
+    """A second download() of the same run launches nothing more and counts nothing again: the (300, 1000, 0.01)
+    case takes the exact tail on its first download, and both downloads give the oracle's corners with one
+    fallback counted.  The same for a detection on the local-maximum route without a presort (Context.gftt
+    with the analytic mask), asked twice."""
+    a, b, _ = pair
+    npts, max_corners, quality = PRESEL_CASES[0]
+    pts = oracle_lib.gftt(a, region_mask(W, H), 300, float(np.float32(0.01)), 30.0)[:npts]
+    prm = vio.default_tracker_params(max_corners=max_corners, seed=5)
+    prm.quality = float(np.float32(quality))
+    klt = vio.default_klt_params()
+    corners = pipeline_oracle(vio, a, b, pts, prm, klt)[3]
+    t = vio.Tracker(gpu_ctx, W, H, max_points=1024, max_corners=1024)
+    t.upload(0, a)
+    t.upload(1, b)
+    t.set_points(pts)
+    t.run(prm, klt)
+    for _ in range(2):
+        res = t.download()
+        assert np.array_equal(res["corners"], corners)
+        assert t.gftt_fallbacks() == (1, 0)
+    t.close()
+    o = oracle_lib.gftt(b, None, 1000, float(np.float32(0.01)), 10.0)
+    for _ in range(2):
+        assert np.array_equal(gpu_ctx.gftt(b, None, 1000, float(np.float32(0.01)), 10.0), o)
+
+
+_PRESEL_VARIANT_CHILD = r"""
+import importlib, sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+vio = importlib.import_module("360_visual_inertial_odometry_amd")
+ref = np.load(sys.argv[2])
+ctx = vio.Context(0)
+klt = vio.default_klt_params()
+for i in range(int(ref["n_cases"])):
+    prm = vio.default_tracker_params(max_corners=int(ref["max_corners"][i]), seed=5)
+    prm.quality = float(ref["quality"][i])
+    t = vio.Tracker(ctx, 960, 480, max_points=1024, max_corners=1024)
+    t.upload(0, ref["a"])
+    t.upload(1, ref["b"])
+    t.set_points(ref["pts%d" % i])
+    t.run(prm, klt)
+    r = t.download()
+    print("CASE", i, np.array_equal(r["kept"], ref["kept%d" % i]), np.array_equal(r["corners"], ref["corners%d" % i]),
+          *t.gftt_fallbacks())
+    t.close()
+ctx.close()
+"""
+
+
+@pytest.fixture(scope="module")
+def presel_default_npz(vio, gpu_ctx, pair, tmp_path_factory):
+    """kept / corners of the five presel cases on the default route (this process), for the variants' children"""
+    a, b, _ = pair
+    pts0 = oracle_lib.gftt(a, region_mask(W, H), 300, float(np.float32(0.01)), 30.0)
+    klt = vio.default_klt_params()
+    d = {"a": a, "b": b, "n_cases": len(PRESEL_CASES), "max_corners": [c[1] for c in PRESEL_CASES],
+         "quality": np.array([c[2] for c in PRESEL_CASES], np.float32)}
+    for i, (npts, max_corners, quality) in enumerate(PRESEL_CASES):
+        prm = vio.default_tracker_params(max_corners=max_corners, seed=5)
+        prm.quality = float(np.float32(quality))
+        t = vio.Tracker(gpu_ctx, W, H, max_points=1024, max_corners=1024)
+        t.upload(0, a)
+        t.upload(1, b)
+        t.set_points(pts0[:npts])
+        t.run(prm, klt)
+        res = t.download()
+        t.close()
+        d["pts%d" % i], d["kept%d" % i], d["corners%d" % i] = pts0[:npts], res["kept"], res["corners"]
+    path = str(tmp_path_factory.mktemp("presel") / "default.npz")
+    np.savez(path, **d)
+    return path
+
+
+@pytest.mark.parametrize("var,fallbacks", [
+    ("VIO_TRK_PRESEL", ["0 0"] * 5),
+    ("VIO_TRK_PRESEL_FLAG", ["1 0", "1 0", "1 0", "0 0", "0 0"]),
+])
+def test_pipeline_retained_alternates_bitwise(presel_default_npz, var, fallbacks):
+    """The two alternates kept as fallbacks -- VIO_TRK_PRESEL=0 (the masked-maximum tail instead of the presort)
+    and VIO_TRK_PRESEL_FLAG=0 (the presort handed over through the stream join) -- give the default route's kept
+    flags and corners bit for bit on the five presel cases.  One child process per variant (the environment is
+    read once per process).  The expected fallback pairs were taken from a run of this test body on the commit
+    before the GfttPlan refactor."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _PRESEL_VARIANT_CHILD, root, presel_default_npz],
+                       env=dict(os.environ, **{var: "0"}), capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    print(r.stdout)
+    cases = [x.split() for x in r.stdout.split("\n") if x.startswith("CASE")]
+    assert len(cases) == len(PRESEL_CASES), r.stdout
+    for i, c in enumerate(cases):
+        assert c[1:4] == [str(i), "True", "True"], r.stdout
+    assert [" ".join(c[4:6]) for c in cases] == fallbacks, r.stdout
+
+
 _PRESEL_TIMEOUT_CHILD = r"""
 import importlib, sys, numpy as np
 sys.path.insert(0, sys.argv[1])
@@ -258,9 +360,9 @@ def test_presel_handoff_timeout_takes_the_exact_tail():
 
 
 def test_pipeline_graph_replay_bitwise(vio, gpu_ctx, synth):
-    """Runs without stage markers (the bench's timed mode; with VIO_TRK_GRAPH=1 captured into a graph
-    and replayed) give bitwise the outputs of a run with them, also after the parameter set and the
-    point count change (config-1 pair at 1920x960)."""
+    """Runs without stage markers (the bench's timed mode), repeated on the same tracker, give bitwise
+    the outputs of a run with them, also after the parameter set and the point count change (config-1
+    pair at 1920x960).  (The name is from when such runs could be captured into a graph and replayed.)"""
     a, b, _ = synth.config1(1920, 960)
     Wf, Hf = 1920, 960
     pts = oracle_lib.gftt(a, region_mask(Wf, Hf), 200, float(np.float32(0.01)), 30.0)
@@ -279,7 +381,7 @@ def test_pipeline_graph_replay_bitwise(vio, gpu_ctx, synth):
 
     prm = vio.default_tracker_params(max_corners=200, seed=1)
     ref = run(prm, pts, True)
-    for _ in range(3):  # capture, then two replays
+    for _ in range(3):
         g = run(prm, pts, False)
         for k in ref:
             assert np.array_equal(ref[k], g[k]), k

@@ -71,7 +71,7 @@ EXPORTS = [
     "vio_window_link_mappoints", "vio_window_add_keyframe", "vio_window_triangulation_candidates",
     "vio_window_commit_triangulation", "vio_window_triangulate", "vio_window_keyframes", "vio_window_num_mappoints",
     "vio_window_mappoint", "vio_window_mappoint_observations", "vio_window_frame_mappoints", "vio_window_map_view",
-    "vio_window_apply_update", "vio_lie_eval",
+    "vio_window_apply_update", "vio_lie_eval", "vio_imu_factor_eval",
 ]
 
 
@@ -138,6 +138,8 @@ def lib():
     L.vio_triangulate_device.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.vio_triangulate_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.vio_lie_eval.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    if hasattr(L, "vio_imu_factor_eval") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        L.vio_imu_factor_eval.argtypes = [vp, C.c_int] + [vp] * 11
     L.vio_load_camera_timestamps.argtypes = [C.c_char_p, vp, C.c_int, C.POINTER(C.c_int)]
     L.vio_load_imu_csv.argtypes = [C.c_char_p, vp, C.c_int, C.POINTER(C.c_int)]
     L.erp_resize_area.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]
@@ -298,6 +300,17 @@ class Context:
         out = np.zeros((max(len(a), 1), no), np.float64)
         self.check(lib().vio_lie_eval(self.h, int(op), _p(a), len(a), _p(out)), "vio_lie_eval")
         return out[:len(a)]
+
+    def imu_factor_eval(self, factors):
+        """vio_imu_factor_eval over a list of factor dicts (abi.imu_factors_to_c); returns a dict of arrays
+        sqrt_info (n,9,9), r / r_wave (n,9), J / J_wave (n,9,12: columns [v_i | bg | ba | v_j])."""
+        n = len(factors)
+        pre, Ti, Tj, arrs = abi.imu_factors_to_c(factors)
+        out = np.zeros((max(n, 1), 315), np.float64)
+        self.check(lib().vio_imu_factor_eval(self.h, n, pre, _p(arrs["gravity"]), Ti, Tj, _p(arrs["delta_i"]),
+                                             _p(arrs["v_i"]), _p(arrs["bg"]), _p(arrs["ba"]), _p(arrs["delta_j"]),
+                                             _p(arrs["v_j"]), _p(out)), "vio_imu_factor_eval")
+        return abi.imu_factor_outputs(out[:n])
 
     def ba_solve(self, problems):
         """Solve a list of BaProblem windows in one launch; returns list of result dicts."""

@@ -161,6 +161,31 @@ def preints_to_c(preints):
     return arr, valid
 
 
+IMU_FACTOR_ARRAYS = (("gravity", 3), ("delta_i", 6), ("v_i", 3), ("bg", 3), ("ba", 3), ("delta_j", 6), ("v_j", 3))
+
+
+def imu_factors_to_c(factors):
+    """list of factor dicts (preint: a preintegration dict as for preints_to_c; T_i / T_j: 4x4 or 3x4 initial
+    poses; gravity, delta_i, v_i, bg, ba, delta_j, v_j) -> (VioPreint array, VioPose array i, VioPose array j,
+    dict of contiguous f64 (n, width) arrays): the arguments of vio_imu_factor_eval / oracle_imu_factor."""
+    n = len(factors)
+    pre, _ = preints_to_c([f["preint"] for f in factors])
+    Ti = poses_to_c(np.array([np.asarray(f["T_i"], np.float64)[:3] for f in factors]).reshape(n, 3, 4))
+    Tj = poses_to_c(np.array([np.asarray(f["T_j"], np.float64)[:3] for f in factors]).reshape(n, 3, 4))
+    arrs = {k: np.ascontiguousarray(np.array([f[k] for f in factors], np.float64).reshape(n, w))
+            for k, w in IMU_FACTOR_ARRAYS}
+    return pre, Ti, Tj, arrs
+
+
+def imu_factor_outputs(out):
+    """(n, 315) rows of vio_imu_factor_eval -> dict of arrays."""
+    out = np.asarray(out, np.float64).reshape(-1, 315)
+    n = len(out)
+    return {"sqrt_info": out[:, :81].reshape(n, 9, 9).copy(), "r": out[:, 81:90].copy(),
+            "J": out[:, 90:198].reshape(n, 9, 12).copy(), "r_wave": out[:, 198:207].copy(),
+            "J_wave": out[:, 207:315].reshape(n, 9, 12).copy()}
+
+
 class BaProblem:
     """Owns numpy buffers + the ctypes struct pointing at them (keeps everything alive)."""
 

@@ -281,7 +281,11 @@ __device__ __noinline__ void imu_eval(const vio_preint& p, const double* sqi, co
 // imu_eval with Jacobians by one whole wave: every lane evaluates the factor's common part (bias
 // correction, raw residual, the weighted rotation residual and Jr^-1 J_Rg), lane i < 9 returns residual
 // row i in r, lane j < 12 writes Jacobian column j (J row-major 9x12, [vi | bg | ba | vj]).  Each output
-// element goes through imu_eval's operations in imu_eval's order (same values); the serial chain of
+// element goes through imu_eval's operations in imu_eval's order in the source, but the two functions are
+// compiled separately and their multiply-adds are not contracted alike: on an MI355X the residual and the
+// vi / ba / vj columns come out bit-identical to imu_eval's, rows 0-2 of the bg columns
+// (-S Jr(-er)^-1 J_Rg) agree with it to rounding only (1 ulp typically, more as Jr(-er) loses condition;
+// tests/test_inertial_factor_gpu.py holds both to the reference's bar).  The serial chain of
 // 486 + 81 dependent multiply-adds becomes 9 + 9 per lane.
 __device__ __forceinline__ void imu_eval_wave_inl(const vio_preint& p, const double* sqi, const double* g, const double* pci,
                                            const double* pcj, const double* vi, const double* bg, const double* ba,
@@ -2232,6 +2236,43 @@ __global__ void lie_ba_kernel(int op, const double* in, double* out, int n) {
 }
 hipError_t launch_lie_ba(int op, const double* in, double* out, int n, hipStream_t stream) {
     hipLaunchKernelGGL(lie_ba_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, op, in, out, n);
+    return hipGetLastError();
+}
+
+// vio_imu_factor_eval (tests): the inertial factor as the solvers evaluate it, one 64-lane workgroup per
+// factor.  The sqrt-information (imu_sqrt_info_wave) and the two pose caches (polar3 of the raw initial
+// rotations as in the solvers' setup, then pose_cache_one) are built in LDS; lane 0 runs the serial
+// imu_eval, the wave runs imu_eval_wave.  st per factor: g(3) dxi_i(6) v_i(3) bg(3) ba(3) dxi_j(6) v_j(3);
+// out per factor: sqrt_info(81) | r(9) | J(108) | r_wave(9) | J_wave(108)
+constexpr int kImuFactorIn = 27, kImuFactorOut = 315;
+__global__ void __launch_bounds__(64) imu_factor_kernel(const vio_preint* pre, const vio_pose* Ti, const vio_pose* Tj,
+                                                        const double* st, double* out) {
+    __shared__ double sqi[81];
+    __shared__ double pinit[2][24];
+    __shared__ double pc[2][36];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const vio_preint& p = pre[f];
+    const double* s = st + (size_t)kImuFactorIn * f;
+    double* o = out + (size_t)kImuFactorOut * f;
+    imu_sqrt_info_wave(p, sqi);
+    if (lane < 2) {
+        const vio_pose& T = lane == 0 ? Ti[f] : Tj[f];
+        polar3(T.R, pinit[lane]);
+        for (int i = 0; i < 3; ++i) pinit[lane][9 + i] = T.t[i];
+        for (int i = 0; i < 9; ++i) pinit[lane][12 + i] = (i % 4 == 0) ? 1.0 : 0.0;  // T_cb: unused here
+        for (int i = 0; i < 3; ++i) pinit[lane][21 + i] = 0.0;
+        pose_cache_one(pinit[lane], s + (lane == 0 ? 3 : 18), pc[lane]);
+    }
+    __syncthreads();
+    for (int e = lane; e < 81; e += 64) o[e] = sqi[e];
+    if (lane == 0) imu_eval(p, sqi, s, pc[0], pc[1], s + 9, s + 12, s + 15, s + 24, true, o + 81, o + 90);
+    double rw = 0.0;
+    imu_eval_wave(p, sqi, s, pc[0], pc[1], s + 9, s + 12, s + 15, s + 24, lane, rw, o + 207);
+    if (lane < 9) o[198 + lane] = rw;
+}
+hipError_t launch_imu_factor(const vio_preint* pre, const vio_pose* Ti, const vio_pose* Tj, const double* st,
+                             double* out, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(imu_factor_kernel, dim3(n), dim3(64), 0, stream, pre, Ti, Tj, st, out);
     return hipGetLastError();
 }
 

@@ -121,6 +121,19 @@ typedef struct {
     double dt_total;
 } vio_preint;
 
+/* Device evaluation of n InertialFactorFixedGravity factors (Factors.cpp:1299-1485) with the device
+   functions the solvers call, for tests against an independent reference: one launch, one 64-lane
+   workgroup per factor.  Per factor f: preint[f], gravity[3f..], the raw (f32 -> f64) initial poses
+   T_wb_i_init[f] / T_wb_j_init[f] (projected as the solvers' setup projects them), the parameter blocks
+   delta_i[6f..] ([rho, phi]), v_i[3f..], bg[3f..], ba[3f..], delta_j[6f..], v_j[3f..].
+   out[315 f ..] = sqrt_info (81, row-major 9x9) | r (9) | J (9x12 row-major, columns [v_i | bg | ba | v_j];
+   the pose Jacobians are identically zero) from the serial evaluation, then r (9) | J (108) from the
+   wave-parallel evaluation. */
+int vio_imu_factor_eval(vio_ctx* ctx, int n, const vio_preint* preint, const double* gravity,
+                        const vio_pose* T_wb_i_init, const vio_pose* T_wb_j_init, const double* delta_i,
+                        const double* v_i, const double* bg, const double* ba, const double* delta_j,
+                        const double* v_j, double* out);
+
 /* which Optimizer entry point the problem mirrors (selects constants and fixing rules) */
 enum {
     VIO_BA_LOCAL = 0, /* RunLocalBA: pose 0 constant (if observed), marginalised MPs constant,

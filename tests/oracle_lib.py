@@ -39,6 +39,24 @@ def ba_solve(vio, prob):
     return O.result()
 
 
+def imu_factor(vio, factors):
+    """oracle_imu_factor over a list of factor dicts (abi.imu_factors_to_c), in the layout of
+    Context.imu_factor_eval: sqrt_info (n,9,9), r (n,9), J (n,9,12: columns [v_i | bg | ba | v_j])."""
+    L = load()
+    L.oracle_imu_factor.argtypes = [C.c_void_p] * 16
+    L.oracle_imu_factor.restype = None
+    n = len(factors)
+    pre, Ti, Tj, a = vio.abi.imu_factors_to_c(factors)
+    out = {"sqrt_info": np.zeros((n, 9, 9)), "r": np.zeros((n, 9)), "J": np.zeros((n, 9, 12))}
+    for f in range(n):
+        J = [np.zeros((9, 3)) for _ in range(4)]
+        L.oracle_imu_factor(C.byref(pre[f]), _p(a["gravity"][f]), C.byref(Ti[f]), C.byref(Tj[f]), _p(a["delta_i"][f]),
+                            _p(a["v_i"][f]), _p(a["bg"][f]), _p(a["ba"][f]), _p(a["delta_j"][f]), _p(a["v_j"][f]),
+                            _p(out["r"][f]), _p(J[0]), _p(J[1]), _p(J[2]), _p(J[3]), _p(out["sqrt_info"][f]))
+        out["J"][f] = np.hstack(J)
+    return out
+
+
 def imu_preintegrate(vio, samples, t_start, t_end, gyro_bias=None, accel_bias=None, noise=None):
     """oracle/imu_oracle.c through the same marshalling as Context.imu_preintegrate."""
     L = load()

@@ -494,8 +494,11 @@ def test_global_vi_parity(vio, synth, gpu_ctx, K, L):
     iterations at the tight bar with the iteration count and step outcomes exact, velocities / biases
     to 1e-6; the converged solve at the reference's options at the VI bar.
 
-    Parity here is pinned to the oracle only: no reference output or fixture covers a VIBA run with
-    more than 10 keyframes.  The oracle's assumptions for it: Ceres SPARSE_SCHUR eliminates the
+    The LM trajectory here is pinned to the oracle only: no reference output or fixture covers a VIBA
+    run with more than 10 keyframes.  What is pinned independently of the oracle is the starting point:
+    the inertial factor itself and the iteration-0 cost and gradient of a 12-keyframe window on this
+    path (tests/test_inertial_factor.py for the oracle, tests/test_inertial_factor_gpu.py for the device,
+    both against tests/inertial_factor_reference.py).  The oracle's assumptions for the rest: Ceres SPARSE_SCHUR eliminates the
     landmarks first (Optimizer.cpp:641 leaves the ordering to Ceres, whose automatic ordering puts
     the independent point blocks in the first group), and the IMU factors' pose Jacobians are zero
     (Factors.cpp:1415-1475), so the reduced system is block diagonal between poses and the

@@ -28,6 +28,7 @@ hipError_t launch_ba_phases(const BaPools& P, const BaWin* hw, int n, hipStream_
 size_t ba_phase_doubles(int K, int L, int N, int T);  // sized for the smallest group (most partials)
 const char* ba_phases_failed_launch();
 hipError_t ba_phases_prepare(const BaWin* hw, int n);
+void ba_schur_lds_info(int K, int L, int T, int gs, int32_t out[3]);
 int ba_cluster_members(const BaWin* hw, int n, int max_per_window);
 hipError_t launch_ba_cluster(const BaPools& P, int n, int C, hipStream_t stream);
 hipError_t ba_cluster_prelaunch(const BaPools& P, int n, hipStream_t stream);
@@ -805,6 +806,12 @@ int vio_ba_walk_geometry(int num_kf, int num_lm, int group_size, int32_t out[5])
     ba_win_set_geometry(w);
     ba_win_set_gs(w, group_size);
     out[0] = w.LC; out[1] = w.nch; out[2] = w.ng; out[3] = w.rK; out[4] = w.rLC;
+    return VIO_OK;
+}
+
+int vio_ba_schur_lds(int num_kf, int num_lm, int tiles, int group_size, int32_t out[3]) {
+    if (num_kf < 1 || num_kf > BA_KMAX || num_lm < 1 || tiles < 1 || tiles > 6 || group_size < 1 || !out) return VIO_EINVAL;
+    ba_schur_lds_info(num_kf, num_lm, tiles, group_size, out);
     return VIO_OK;
 }
 

@@ -238,7 +238,13 @@ __device__ inline bool ph_skip(const BaPools& P, int wi) { return P.win[wi].is_p
 // the window of a per-window (x) / per-window-row (y) workgroup: a launch covers the windows
 // [win_base, win_base + grid extent) of the batch (one sub-batch per stream, launch_ba_phases)
 __device__ inline int ph_wx(const BaPools& P) { return P.win_base + (int)blockIdx.x; }
-__device__ inline int ph_wy(const BaPools& P) { return P.win_base + (int)blockIdx.y; }
+// A per-window-row launch of `per` workgroups for each of n windows has the grid (gx, per, n / gx) of ph_grid,
+// gx = 8 where n % 8 == 0: linear block ids (x fastest) are dealt round robin over the 8 XCDs, so every
+// workgroup of local window i = x + gx z runs on XCD i % 8, where the window's ph_prep / ph_solve workgroup
+// (block i of n) reads its partials; any other n: gx = 1, the plain (per, n) order.  Placement only: nothing
+// relies on it.  ph_sub: the workgroup's chunk / group index within its window
+__device__ inline int ph_wy(const BaPools& P) { return P.win_base + (int)(blockIdx.x + gridDim.x * blockIdx.z); }
+__device__ inline int ph_sub() { return (int)blockIdx.y; }
 
 // the cluster leader's LDS copy of its window's PhState: right after the leader's BaShared and PhClusterSh in
 // the kernel's dynamic LDS (ph_cluster_lds_bytes)
@@ -601,7 +607,7 @@ __global__ void __launch_bounds__(BA_THREADS) ph_lin_kernel(BaPools P) {
     __shared__ PhShared sh;
     const PhState& gst = *ph_ctx(P, wi, 0).gs;
     if (gst.st.done || !gst.need_lin || !gst.first) return;
-    ph_lin_body<false>(P, wi, (int)blockIdx.x, sh);
+    ph_lin_body<false>(P, wi, ph_sub(), sh);
 }
 #endif
 
@@ -1054,9 +1060,72 @@ __global__ void __launch_bounds__(BA_THREADS) ph_prep_kernel(BaPools P) {
 // the cluster route's one-barrier wave combine of a Schur group (ph_schur_body): four partial areas of
 // NT 256 + 16 T doubles in the member's dynamic LDS (what follows PhSchurSh inside the kernel's BaShared-sized
 // allotment); larger tile counts keep the wave-by-wave combine
+//
+// ST, the phase route's staged instance (ph_schur_staged_doubles: where two workgroups per CU still fit):
+// the group's per-landmark values stay in LDS instead of coming back through memory once per chunk and
+// keyframe lane.  The thread that factors landmark slot s = l - lbeg of the group keeps s_l and L^-1 in
+// gcol[gsc KC + i GL + s] (i < 9, GL = gsc LC slots, gsc = min(gs, nch) chunks) and forms the slot's rhs
+// entries h = L^-1 (g s) once, at gcol[KC chunk + 3 j] (every chunk's column padded to KC with zeros); the
+// fill and the MFMA phase read them there, and the prefetch carries the observation's own values only.
+// The four waves' partials are combined with two barriers: waves 0 and 1 write theirs to two areas over
+// the dead panel, wave 2 folds both and its own into the first, wave 3 adds its own and writes the group's
+// partials to memory from its MFMA layout (64 contiguous doubles per tile row).  Every expression and every
+// summation order is that of the unstaged form: bitwise the same partials.
+// The staged instance's combine of the four waves' partials (acc: the wave's lower tiles in MFMA layout, bacc:
+// its rhs rows, already summed over the wave's k-lanes) with two barriers: waves 0 and 1 write theirs to two
+// areas of E = NT 256 + 16 T doubles at comb (the dead panel), wave 2 folds both and its own into the first,
+// wave 3 adds its own and writes the group's partials to sp from its MFMA layout (tile t, row 4e+kk, col r16 is
+// element 256 t + 64 e + lane: 64 contiguous doubles per wave and store).  Every element is summed
+// (((0 + p0) + p1) + p2) + p3, the order of the wave-by-wave combine.
+template <int T, bool WT>
+__device__ __forceinline__ void ph_schur_combine2(const d4* acc, const double* bacc, double* comb, double* sp) {
+    static_assert(BA_THREADS / 64 == 4, "written for four waves");
+    constexpr int NT = T * (T + 1) / 2, E = NT * 256 + 16 * T;
+    const int wid = wave_id(), lane = threadIdx.x & 63, r16 = lane & 15, kk = lane >> 4;
+    if (wid < 2) {
+        double* mine = comb + wid * E;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) mine[t * 256 + 64 * e + lane] = acc[t][e];
+#pragma unroll
+        for (int r = 0; r < T; ++r)
+            if (kk == 0) mine[NT * 256 + 16 * r + r16] = bacc[r];
+    }
+    __syncthreads();
+    if (wid == 2) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                double* d = comb + t * 256 + 64 * e + lane;
+                *d = ((0.0 + *d) + d[E]) + acc[t][e];
+            }
+#pragma unroll
+        for (int r = 0; r < T; ++r) {
+            double* d = comb + NT * 256 + 16 * r + r16;
+            if (kk == 0) *d = ((0.0 + *d) + d[E]) + bacc[r];
+        }
+    }
+    __syncthreads();
+    if (wid == 3) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = t * 256 + 64 * e + lane;
+                st_w<WT>(sp + i, comb[i] + acc[t][e]);
+            }
+#pragma unroll
+        for (int r = 0; r < T; ++r) {
+            const int i = NT * 256 + 16 * r + r16;
+            if (kk == 0) st_w<WT>(sp + i, comb[i] + bacc[r]);
+        }
+    }
+}
 struct PhSchurSh;
 __host__ __device__ constexpr bool ph_schur_fast_combine(int T);
-template <int T, bool WT = true>
+template <int T, bool WT = true, bool ST = false>
 __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double radius, double* Zt, double* gcol,
                                               const int* posef, const double* s_f, const double* rlin_k,
                                               const double* rcb_k, double* red, double* redm, PhStamp& stamp) {
@@ -1079,13 +1148,100 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
     const double* xl = x.xl;
     const int* lk = reinterpret_cast<const int*>(ws + c.L.lk);
     const int lbeg = gi * w.gs * LC, lend = min(L, lbeg + w.gs * LC);
+    const int jf = threadIdx.x / K, kf = threadIdx.x - jf * K;
+    const int pf = jf < LC ? posef[kf] : -1;
+    // the fill inputs of a lane are loaded one chunk ahead (in flight during the previous chunk's
+    // MFMA phase), its observation index two chunks ahead: no global round trip between barriers
+    auto obs_of = [&](int l0c) -> int {
+        const int l = l0c + jf;
+        return (pf >= 0 && l0c < lend && l < min(l0c + LC, L)) ? lk[16 * l + kf] : -1;
+    };
+    double pas, ppw[3], psv[3], pli[6];
+    double hg[3], hs[3], hl[6];  // the rhs column's inputs (lanes < LC: landmark l0c + lane), likewise ahead
+    bool pon = false, hon = false;
+    auto fetch_at = [&](int l, int o, bool var) {
+        pon = var;
+        if (pon) {
+            pas = as[o];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) ppw[i] = xl[3 * l + i];
+            if constexpr (!ST) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) psv[i] = sl[(int64_t)i * L + l];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) pli[i] = Li[(int64_t)i * L + l];
+            }
+        }
+    };
+    auto fetch = [&](int l0c, int o) {
+        const int l = l0c + jf;
+        fetch_at(l, o, o >= 0 && c.lm_var[l]);
+        if constexpr (!ST) {
+            const int lg = l0c + (int)threadIdx.x;
+            hon = (int)threadIdx.x < LC && lg < min(l0c + LC, L) && c.lm_var[lg];
+            if (T <= 4 && hon) {  // (larger tile counts: no registers to spare, loaded in the chunk's turn)
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    hg[i] = gl[(int64_t)i * L + lg];
+                    hs[i] = sl[(int64_t)i * L + lg];
+                }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) hl[i] = Li[(int64_t)i * L + lg];
+            }
+        }
+    };
+    const int gsc = min(w.gs, w.nch), GL = gsc * LC;  // staged: chunks and landmark slots of a group
+    double* sst = gcol + gsc * KC;
+    // staged: the lane's landmark values of chunk l0c from the group's LDS copy (into registers a chunk ahead,
+    // like the rest of the fill's inputs: the fill itself then waits for no LDS read)
+    auto staged = [&](int l0c) {
+        if (pon) {
+            const double* sv = sst + (l0c - lbeg + jf);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) psv[i] = sv[i * GL];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) pli[i] = sv[(3 + i) * GL];
+        }
+    };
+    // staged: nothing the first fill reads from memory waits for the landmark blocks -- the first two chunks'
+    // observation indices and the first chunk's landmark flags are requested with the blocks' own inputs, the
+    // observation's values as soon as its index is there, and arrive while the blocks are factored
+    int o_nxt = -1, o_first = -1, var_first = 0;
+    bool first_done = !ST;
+    if constexpr (ST) {
+        o_first = obs_of(lbeg);
+        o_nxt = obs_of(lbeg + LC);
+        var_first = c.lm_var[min(lbeg + jf, L - 1)];
+        // the panel is zeroed under those loads; the barriers of the blocks' reduction order it before the fills
+        for (int e = threadIdx.x; e < KC * KS; e += BA_THREADS) Zt[e] = 0.0;
+    }
     // (1) landmark blocks of the group
     int bad = 0;
-    for (int l = lbeg + threadIdx.x; l < lend; l += BA_THREADS) {
-        if (!c.lm_var[l]) continue;
-        const double s0 = sl[l], s1 = sl[(int64_t)L + l], s2 = sl[2 * (int64_t)L + l];
-        double v[6];
-        for (int i = 0; i < 6; ++i) v[i] = V[(int64_t)i * L + l];
+    for (int l = lbeg + threadIdx.x; l < (ST ? lbeg + GL : lend); l += BA_THREADS) {
+        double s0, s1, s2, v[6], g[3];
+        double* hc = nullptr;
+        if constexpr (ST) {
+            // every slot's rhs entries and its chunk's padding start at zero; the loads in one batch
+            const int s = l - lbeg, ci = walk_div(s, w.rLC), j = s - ci * LC;
+            hc = gcol + ci * KC + 3 * j;
+            hc[0] = hc[1] = hc[2] = 0.0;
+            if (j == LC - 1)
+                for (int e = 3 * LC; e < KC; ++e) gcol[ci * KC + e] = 0.0;
+            const int lq = min(l, lend - 1);
+            const int var = c.lm_var[lq];
+            s0 = sl[lq], s1 = sl[(int64_t)L + lq], s2 = sl[2 * (int64_t)L + lq];
+            for (int i = 0; i < 6; ++i) v[i] = V[(int64_t)i * L + lq];
+            for (int i = 0; i < 3; ++i) g[i] = gl[(int64_t)i * L + lq];
+            if (!first_done) {
+                fetch_at(lbeg + jf, o_first, o_first >= 0 && var_first);
+                first_done = true;
+            }
+            if (l >= lend || !var) continue;
+        } else {
+            if (!c.lm_var[l]) continue;
+            s0 = sl[l], s1 = sl[(int64_t)L + l], s2 = sl[2 * (int64_t)L + l];
+            for (int i = 0; i < 6; ++i) v[i] = V[(int64_t)i * L + l];
+        }
         double a00 = v[0] * s0 * s0, a01 = v[1] * s0 * s1, a02 = v[2] * s0 * s2;
         double a11 = v[3] * s1 * s1, a12 = v[4] * s1 * s2, a22 = v[5] * s2 * s2;
         a00 += fmin(fmax(a00, 1e-6), 1e32) / radius;
@@ -1108,7 +1264,20 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
         Li[(int64_t)3 * L + l] = i20;
         Li[(int64_t)4 * L + l] = i21;
         Li[(int64_t)5 * L + l] = i22;
+        if constexpr (ST) {
+            double* sv = sst + (l - lbeg);
+            sv[0] = s0; sv[GL] = s1; sv[2 * GL] = s2;
+            sv[3 * GL] = i00; sv[4 * GL] = i10; sv[5 * GL] = i11;
+            sv[6 * GL] = i20; sv[7 * GL] = i21; sv[8 * GL] = i22;
+            const double g0 = g[0] * s0, g1 = g[1] * s1, g2 = g[2] * s2;
+            // h = L^-1 (g s) with the fused operations spelled out, as every unstaged instance contracts the
+            // per-chunk expressions below (left to the compiler here, h1 came out with the other product fused)
+            hc[0] = i00 * g0;
+            hc[1] = fma(i10, g0, i11 * g1);
+            hc[2] = fma(i22, g2, fma(i20, g0, i21 * g1));
+        }
     }
+    if (!first_done) fetch_at(lbeg + jf, o_first, o_first >= 0 && var_first);  // (a thread without a slot)
     const double anybad = block_max((double)bad, redm);
     if (threadIdx.x == 0) st_w<WT>(x.pr + x.ph.bpart + 8 * gi, anybad);
     stamp(6);
@@ -1119,50 +1288,22 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
     double bacc[T];
 #pragma unroll
     for (int r = 0; r < T; ++r) bacc[r] = 0.0;
-    const int jf = threadIdx.x / K, kf = threadIdx.x - jf * K;
-    const int pf = jf < LC ? posef[kf] : -1;
     const double* rbw = rlin_k + PL24 * (kf < BA_KMAX ? kf : 0);  // LDS (keeps the fill's registers low)
     const double* rcb = rcb_k + 9 * (kf < BA_KMAX ? kf : 0);
-    for (int e = threadIdx.x; e < KC * KS; e += BA_THREADS) Zt[e] = 0.0;
-    for (int e = threadIdx.x; e < KC; e += BA_THREADS) gcol[e] = 0.0;
-    __syncthreads();
+    if constexpr (!ST) {
+        for (int e = threadIdx.x; e < KC * KS; e += BA_THREADS) Zt[e] = 0.0;
+        for (int e = threadIdx.x; e < KC; e += BA_THREADS) gcol[e] = 0.0;
+        __syncthreads();
+    }
     stamp(15);
     if (!anybad) {
-        // the fill inputs of a lane are loaded one chunk ahead (in flight during the previous chunk's
-        // MFMA phase), its observation index two chunks ahead: no global round trip between barriers
-        auto obs_of = [&](int l0c) -> int {
-            const int l = l0c + jf;
-            return (pf >= 0 && l0c < lend && l < min(l0c + LC, L)) ? lk[16 * l + kf] : -1;
-        };
-        double pas, ppw[3], psv[3], pli[6];
-        double hg[3], hs[3], hl[6];  // the rhs column's inputs (lanes < LC: landmark l0c + lane), likewise ahead
-        bool pon = false, hon = false;
-        auto fetch = [&](int l0c, int o) {
-            const int l = l0c + jf;
-            pon = o >= 0 && c.lm_var[l];
-            if (pon) {
-                pas = as[o];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) ppw[i] = xl[3 * l + i];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) psv[i] = sl[(int64_t)i * L + l];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) pli[i] = Li[(int64_t)i * L + l];
-            }
-            const int lg = l0c + (int)threadIdx.x;
-            hon = (int)threadIdx.x < LC && lg < min(l0c + LC, L) && c.lm_var[lg];
-            if (T <= 4 && hon) {  // (larger tile counts: no registers to spare, loaded in the chunk's turn)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    hg[i] = gl[(int64_t)i * L + lg];
-                    hs[i] = sl[(int64_t)i * L + lg];
-                }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) hl[i] = Li[(int64_t)i * L + lg];
-            }
-        };
-        fetch(lbeg, obs_of(lbeg));
-        int o_nxt = obs_of(lbeg + LC);
+        if constexpr (ST) {
+            staged(lbeg);
+        } else {
+            fetch(lbeg, obs_of(lbeg));
+            o_nxt = obs_of(lbeg + LC);
+        }
+        const double* gch = gcol;  // the chunk's rhs column
         for (int l0 = lbeg; l0 < lend; l0 += LC) {
             const int l1 = min(l0 + LC, L);
             // fill
@@ -1190,7 +1331,7 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
                         for (int i = 0; i < 6; ++i) zt[cc * KS + i] = 0.0;
                 }
             }
-            if ((int)threadIdx.x < LC) {
+            if (!ST && (int)threadIdx.x < LC) {
                 double h0 = 0.0, h1 = 0.0, h2 = 0.0;
                 if (hon) {
                     if constexpr (T > 4) {
@@ -1218,6 +1359,7 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
             stamp(7);
             if (l0 + LC < lend) {  // the next chunk's inputs, loading while this chunk's MFMAs run
                 fetch(l0 + LC, o_nxt);
+                if constexpr (ST) staged(l0 + LC);
                 o_nxt = obs_of(l0 + 2 * LC);
             }
             const int nsteps = (3 * (l1 - l0) + 3) >> 2;
@@ -1226,7 +1368,7 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
                 double f[T];
 #pragma unroll
                 for (int r = 0; r < T; ++r) f[r] = Zt[kr + 16 * r + r16];
-                const double gq = gcol[4 * st + kk];
+                const double gq = gch[4 * st + kk];
 #pragma unroll
                 for (int r = 0, t = 0; r < T; ++r)
 #pragma unroll
@@ -1236,10 +1378,11 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
             }
             __syncthreads();
             stamp(13);
+            if constexpr (ST) gch += KC;
         }
     }
     // combine the 4 waves' partials in order (in LDS, over the dead panel), then one global write
-    __syncthreads();
+    if constexpr (!ST) __syncthreads();  // (staged: the last barrier above, on either path, already ended every use)
     double* comb = Zt;
 #pragma unroll
     for (int r = 0; r < T; ++r) {
@@ -1268,6 +1411,11 @@ __device__ __forceinline__ void ph_schur_body(const PhCtx& x, int gi, double rad
             for (int wv = 0; wv < NW; ++wv) v += *reinterpret_cast<const ph_d2*>(comb + wv * E + e);
             st_x2(rs, e, v);
         }
+        stamp(14);
+        return;
+    }
+    if constexpr (ST) {
+        ph_schur_combine2<T, WT>(acc, bacc, comb, x.pr + x.ph.spart + (int64_t)gi * E);
         stamp(14);
         return;
     }
@@ -1323,6 +1471,22 @@ __host__ __device__ constexpr bool ph_schur_fast_combine(int T) {
     return ((sizeof(PhSchurSh) + 15) & ~(size_t)15) + sizeof(double) * (BA_THREADS / 64) * (T * (T + 1) / 2 * 256 + 16 * T) <=
            sizeof(BaShared);
 }
+// The staged instance of ph_schur_kernel (ph_schur_body's ST) for a window's tile count, chunk size and
+// chunks per group gsc = min(gs, nch): its dynamic LDS in doubles -- the panel, the group's rhs columns
+// (gsc KC) and landmark values (9 gsc LC), or the two combine areas where those are larger -- or 0 where
+// the instance does not apply: T = 6 (its combine areas alone exceed the panel's allotment), or two
+// workgroups per CU no longer fit the CU's 160 KB (each workgroup's static + dynamic LDS rounded up to 2 KB,
+// above any allocation granule).  Without two workgroups a CU's matrix cores idle through every fill.
+constexpr int PH_LDS_CU = 160 * 1024, PH_LDS_ROUND = 2048;
+__host__ __device__ inline int ph_schur_staged_doubles(int T, int LC, int gsc) {
+    if (T < 1 || T > 5 || gsc < 1) return 0;
+    const int KC = schur_kc(LC);
+    const int64_t a = (int64_t)KC * schur_ks(T) + (int64_t)gsc * KC + (int64_t)9 * gsc * LC;
+    const int64_t b = 2 * (T * (T + 1) / 2 * 256 + 16 * T);
+    const int64_t d = a > b ? a : b;
+    const int64_t wg = ((int64_t)sizeof(PhSchurSh) + 8 * d + PH_LDS_ROUND - 1) / PH_LDS_ROUND * PH_LDS_ROUND;
+    return 2 * wg <= PH_LDS_CU && (int64_t)gsc * LC < WALK_TMAX ? (int)d : 0;
+}
 __device__ __forceinline__ void ph_schur_inputs(PhSchurSh& ss, const PhCtx& x, const double* rlin) {
     const BaWin& w = *x.c.w;
     for (int k = threadIdx.x; k < BA_KMAX; k += BA_THREADS) ss.posef[k] = k < w.K ? w.pose_f[k] : -1;
@@ -1335,7 +1499,7 @@ __device__ __forceinline__ void ph_schur_inputs(PhSchurSh& ss, const PhCtx& x, c
     for (int e = threadIdx.x; e < 9 * w.K; e += BA_THREADS) ss.rcb[e] = x.pr[x.ph.rcb + e];
 }
 // group gi of window x at trust-region radius `radius`; dyn: the panel LDS (ph_schur_lds_doubles)
-template <int TI, bool WT = true>
+template <int TI, bool WT = true, bool ST = false>
 __device__ __forceinline__ void ph_schur_group(const BaPools& P, const PhCtx& x, int wi, int gi, double radius,
                                                PhSchurSh& ss, double* dyn) {
     const BaWin& w = *x.c.w;
@@ -1345,45 +1509,64 @@ __device__ __forceinline__ void ph_schur_group(const BaPools& P, const PhCtx& x,
     // diagnostic slots (group 0 of each window): 6 landmark blocks, 15 panel zeroing, 7 fills, 13 MFMA
     // phases, 14 wave combine + partial write
     PhStamp stamp(gi == 0 ? P.prof : nullptr, wi);
-    ph_schur_body<TI, WT>(x, gi, radius, Zt, gcol, ss.posef, ss.s_f, ss.rlin, ss.rcb, ss.red, ss.redm, stamp);
+    ph_schur_body<TI, WT, ST>(x, gi, radius, Zt, gcol, ss.posef, ss.s_f, ss.rlin, ss.rcb, ss.red, ss.redm, stamp);
 }
 #ifndef VIO_BA_CLUSTER_TU
-template <int TI>
+// ST: the staged instance (every window of the launch's tile count fits it, ph_extents).  Its head asks for
+// the LM state and the small inputs, none of whose addresses depend on the state, in one round trip, and
+// selects the current parameter set's view afterwards
+template <int TI, bool ST>
 __global__ void __launch_bounds__(BA_THREADS, PH_SCHUR_OCC) ph_schur_kernel(BaPools P) {
     const int wi = ph_wy(P);
     if (ph_skip(P, wi) || ph_schur_t(P.win[wi].T) != TI) return;
     extern __shared__ __align__(16) double ph_dyn[];
     __shared__ PhSchurSh ss;
-    const PhCtx x = ph_ctx(P, wi);
-    if ((int)blockIdx.x >= x.ph.ng) return;
-    if (x.gs->st.done) return;
-    ph_schur_inputs(ss, x, nullptr);
-    __syncthreads();
-    ph_schur_group<TI, false>(P, x, wi, (int)blockIdx.x, x.gs->st.radius, ss, ph_dyn);
-}
-#endif
-#ifndef VIO_BA_CLUSTER_TU
-static const void* ph_schur_fn(int TI) {
-    switch (TI) {
-        case 1: return (const void*)ph_schur_kernel<1>;
-        case 2: return (const void*)ph_schur_kernel<2>;
-        case 3: return (const void*)ph_schur_kernel<3>;
-        case 4: return (const void*)ph_schur_kernel<4>;
-        case 5: return (const void*)ph_schur_kernel<5>;
-        default: return (const void*)ph_schur_kernel<6>;
+    if constexpr (ST) {
+        const PhCtx x0 = ph_ctx(P, wi, 0);
+        if (ph_sub() >= x0.ph.ng) return;
+        const int cur = x0.gs->cur, done = x0.gs->st.done;
+        const double radius = x0.gs->st.radius;
+        ph_schur_inputs(ss, x0, nullptr);
+        if (done) return;
+        __syncthreads();
+        ph_schur_group<TI, false, true>(P, ph_ctx_at(x0, cur), wi, ph_sub(), radius, ss, ph_dyn);
+    } else {
+        const PhCtx x = ph_ctx(P, wi);
+        if (ph_sub() >= x.ph.ng) return;
+        if (x.gs->st.done) return;
+        ph_schur_inputs(ss, x, nullptr);
+        __syncthreads();
+        ph_schur_group<TI, false>(P, x, wi, ph_sub(), x.gs->st.radius, ss, ph_dyn);
     }
 }
-#endif
-#ifndef VIO_BA_CLUSTER_TU
-static void ph_schur_launch(int TI, dim3 grid, size_t lds, hipStream_t stream, const BaPools& P) {
+template <bool ST>
+static const void* ph_schur_fn_of(int TI) {
     switch (TI) {
-        case 1: hipLaunchKernelGGL(ph_schur_kernel<1>, grid, dim3(BA_THREADS), lds, stream, P); break;
-        case 2: hipLaunchKernelGGL(ph_schur_kernel<2>, grid, dim3(BA_THREADS), lds, stream, P); break;
-        case 3: hipLaunchKernelGGL(ph_schur_kernel<3>, grid, dim3(BA_THREADS), lds, stream, P); break;
-        case 4: hipLaunchKernelGGL(ph_schur_kernel<4>, grid, dim3(BA_THREADS), lds, stream, P); break;
-        case 5: hipLaunchKernelGGL(ph_schur_kernel<5>, grid, dim3(BA_THREADS), lds, stream, P); break;
-        default: hipLaunchKernelGGL(ph_schur_kernel<6>, grid, dim3(BA_THREADS), lds, stream, P); break;
+        case 1: return (const void*)ph_schur_kernel<1, ST>;
+        case 2: return (const void*)ph_schur_kernel<2, ST>;
+        case 3: return (const void*)ph_schur_kernel<3, ST>;
+        case 4: return (const void*)ph_schur_kernel<4, ST>;
+        case 5: return (const void*)ph_schur_kernel<5, ST>;
+        default: return ST ? nullptr : (const void*)ph_schur_kernel<6, false>;  // (no staged instance of 6)
     }
+}
+static const void* ph_schur_fn(int TI, bool staged) { return staged ? ph_schur_fn_of<true>(TI) : ph_schur_fn_of<false>(TI); }
+template <bool ST>
+static void ph_schur_launch_of(int TI, dim3 grid, size_t lds, hipStream_t stream, const BaPools& P) {
+    switch (TI) {
+        case 1: hipLaunchKernelGGL((ph_schur_kernel<1, ST>), grid, dim3(BA_THREADS), lds, stream, P); break;
+        case 2: hipLaunchKernelGGL((ph_schur_kernel<2, ST>), grid, dim3(BA_THREADS), lds, stream, P); break;
+        case 3: hipLaunchKernelGGL((ph_schur_kernel<3, ST>), grid, dim3(BA_THREADS), lds, stream, P); break;
+        case 4: hipLaunchKernelGGL((ph_schur_kernel<4, ST>), grid, dim3(BA_THREADS), lds, stream, P); break;
+        case 5: hipLaunchKernelGGL((ph_schur_kernel<5, ST>), grid, dim3(BA_THREADS), lds, stream, P); break;
+        default:
+            if constexpr (!ST) hipLaunchKernelGGL((ph_schur_kernel<6, false>), grid, dim3(BA_THREADS), lds, stream, P);
+            break;
+    }
+}
+static void ph_schur_launch(int TI, bool staged, dim3 grid, size_t lds, hipStream_t stream, const BaPools& P) {
+    if (staged) ph_schur_launch_of<true>(TI, grid, lds, stream, P);
+    else ph_schur_launch_of<false>(TI, grid, lds, stream, P);
 }
 #endif
 
@@ -2248,7 +2431,7 @@ __device__ __forceinline__ void ph_back_launch(const BaPools& P, PhShared& sh) {
     // other inputs depend on the current parameter set, i.e. on the state)
     const BaWin& w0 = *x0.c.w;
     const Walk g0 = walk_geom(w0);
-    const int ci = (int)blockIdx.x, l = ci * g0.LC + g0.jf;
+    const int ci = ph_sub(), l = ci * g0.LC + g0.jf;
     const int o_pre = (g0.on && ci < x0.ph.nch && l < w0.L)
                           ? reinterpret_cast<const int*>(x0.c.ws + x0.c.L.lk)[16 * l + g0.kf] : -1;
     const PhState& gst = *x0.gs;
@@ -2775,10 +2958,18 @@ __global__ void __launch_bounds__(BA_THREADS, 1) ph_cluster_kernel(BaPools P, in
 size_t ba_phase_doubles(int K, int L, int N, int T) { return (size_t)ph_layout(K, L, N, T, PH_GS_MIN).total; }
 
 static const char* ph_last_failed = "";
-// grid extents of a batch; per Schur instance (tile count) its largest dynamic LDS (0: unused)
-static void ph_extents(const BaWin* hw, int n, int& slots, int& nch_max, int& ng_max, int* lds_t) {
+// per Schur instance (tile count) of a batch: the largest dynamic LDS in doubles of the unstaged kernel over
+// all its windows (0: tile count unused) and of the staged kernel over the windows that fit it, and whether a
+// launch over these windows takes the staged instance: where every one of them fits it
+struct PhSchurPlan {
+    int lds_u[7], lds_s[7];
+    bool staged[7];
+    size_t bytes(int t) const { return sizeof(double) * (size_t)(staged[t] ? lds_s[t] : lds_u[t]); }
+};
+// grid extents of a batch and its Schur plan
+static void ph_extents(const BaWin* hw, int n, int& slots, int& nch_max, int& ng_max, PhSchurPlan& sp) {
     slots = 1; nch_max = 1; ng_max = 1;
-    for (int t = 0; t <= 6; ++t) lds_t[t] = 0;
+    for (int t = 0; t <= 6; ++t) sp.lds_u[t] = sp.lds_s[t] = 0, sp.staged[t] = true;
     for (int i = 0; i < n; ++i) {
         const PhLayout pl = ph_layout(hw[i].K, hw[i].L, hw[i].N, hw[i].T, hw[i].gs);
         slots = std::max(slots, hw[i].max_iter + 1);
@@ -2786,16 +2977,38 @@ static void ph_extents(const BaWin* hw, int n, int& slots, int& nch_max, int& ng
         ng_max = std::max(ng_max, pl.ng);
         if (!hw[i].is_pnp) {
             const int ti = ph_schur_t(hw[i].T);
-            lds_t[ti] = std::max(lds_t[ti], ph_schur_lds_doubles(hw[i].T, pl.LC));
+            sp.lds_u[ti] = std::max(sp.lds_u[ti], ph_schur_lds_doubles(hw[i].T, pl.LC));
+            const int sd = ph_schur_staged_doubles(hw[i].T, pl.LC, std::min(hw[i].gs, pl.nch));
+            sp.lds_s[ti] = std::max(sp.lds_s[ti], sd);
+            if (!sd) sp.staged[ti] = false;
         }
     }
+    for (int t = 0; t <= 6; ++t) sp.staged[t] = sp.staged[t] && sp.lds_s[t] > 0;
 }
-// kernel attributes (dynamic LDS limits) for a batch: set outside any stream capture
+// ph_schur's LDS for one window shape (tests): out = { dynamic bytes, static bytes, staged instance taken }
+void ba_schur_lds_info(int K, int L, int T, int gs, int32_t out[3]) {
+    BaWin w{};
+    w.K = K; w.L = L; w.T = T; w.max_iter = 1;
+    ba_win_set_geometry(w);
+    ba_win_set_gs(w, gs);
+    int slots, nch_max, ng_max;
+    PhSchurPlan sp;
+    ph_extents(&w, 1, slots, nch_max, ng_max, sp);
+    const int ti = ph_schur_t(T);
+    out[0] = (int32_t)sp.bytes(ti);
+    out[1] = (int32_t)sizeof(PhSchurSh);
+    out[2] = sp.staged[ti] ? 1 : 0;
+}
+// kernel attributes (dynamic LDS limits) for a batch: set outside any stream capture.  Both instances of a tile
+// count get theirs -- the unstaged one for the batch's largest panel, the staged one for the largest staged
+// size among the windows that fit it: a sub-batch of the batch (launch_ba_phases) decides for its own windows,
+// and whichever instance it takes then needs no more than was set here
 hipError_t ba_phases_prepare(const BaWin* hw, int n) {
-    int slots, nch_max, ng_max, lds_t[7];
-    ph_extents(hw, n, slots, nch_max, ng_max, lds_t);
+    int slots, nch_max, ng_max;
+    PhSchurPlan sp;
+    ph_extents(hw, n, slots, nch_max, ng_max, sp);
     static bool attr_set[kMaxDevices] = {};
-    static size_t schur_attr[kMaxDevices][7] = {};
+    static size_t schur_attr[kMaxDevices][7][2] = {};
     std::lock_guard<std::mutex> lock(g_attr_mutex);  // see launch_ba_windows
     const int dev = current_device();
     if (!attr_set[dev]) {
@@ -2804,14 +3017,15 @@ hipError_t ba_phases_prepare(const BaWin* hw, int n) {
         if (e != hipSuccess) return e;
         attr_set[dev] = true;
     }
-    for (int t = 1; t <= 6; ++t) {
-        const size_t schur_lds = sizeof(double) * (size_t)lds_t[t];
-        if (schur_lds > schur_attr[dev][t]) {
-            hipError_t e = hipFuncSetAttribute(ph_schur_fn(t), hipFuncAttributeMaxDynamicSharedMemorySize, (int)schur_lds);
-            if (e != hipSuccess) return e;
-            schur_attr[dev][t] = schur_lds;
+    for (int t = 1; t <= 6; ++t)
+        for (int st = 0; st < 2; ++st) {
+            const size_t schur_lds = sizeof(double) * (size_t)(st ? sp.lds_s[t] : sp.lds_u[t]);
+            if (schur_lds > schur_attr[dev][t][st]) {
+                hipError_t e = hipFuncSetAttribute(ph_schur_fn(t, st != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)schur_lds);
+                if (e != hipSuccess) return e;
+                schur_attr[dev][t][st] = schur_lds;
+            }
         }
-    }
     return hipSuccess;
 }
 const char* ba_phases_failed_launch() { return ph_last_failed; }
@@ -2882,9 +3096,18 @@ hipError_t launch_ba_cluster(const BaPools& P, int n, int C, hipStream_t stream)
 #ifndef VIO_BA_CLUSTER_TU
 // the phase sequence of the windows [P.win_base, P.win_base + n) on one stream; hw: host copy of the
 // packed window descriptors of those windows (grid extents and LDS sizes come from them)
+static dim3 ph_grid(int per, int n) {
+    static const bool plain = [] {
+        const char* v = std::getenv("VIO_BA_XCD_ROWS");  // experiment override: 0 = the plain (per, n) order
+        return v && v[0] == '0';
+    }();
+    const int gx = !plain && n % 8 == 0 ? 8 : 1;
+    return dim3(gx, per, n / gx);
+}
 static hipError_t launch_ba_phase_seq(const BaPools& P, const BaWin* hw, int n, hipStream_t stream) {
-    int slots, nch_max, ng_max, lds_t[7];
-    ph_extents(hw, n, slots, nch_max, ng_max, lds_t);
+    int slots, nch_max, ng_max;
+    PhSchurPlan sp;
+    ph_extents(hw, n, slots, nch_max, ng_max, sp);
     hipError_t e;
 #define PH_CHECK(what)                                                             \
     if ((e = hipGetLastError()) != hipSuccess) {                                   \
@@ -2899,19 +3122,19 @@ static hipError_t launch_ba_phase_seq(const BaPools& P, const BaWin* hw, int n, 
         // (measured and not kept: the step control as its own launch with ph_prep beside the Schur groups,
         // 305 -> 345 us per iteration at 256 windows -- the long Schur workgroups then wait for slots)
         if (s == 0) {  // later linearisations come from ph_back (the accepted candidate's)
-            hipLaunchKernelGGL(ph_lin_kernel, dim3(nch_max, n), dim3(BA_THREADS), 0, stream, P);
+            hipLaunchKernelGGL(ph_lin_kernel, ph_grid(nch_max, n), dim3(BA_THREADS), 0, stream, P);
             PH_CHECK("ph_lin_kernel");
         }
         hipLaunchKernelGGL(ph_prep_kernel, dim3(n), dim3(BA_THREADS), 0, stream, P);
         PH_CHECK("ph_prep_kernel");
         if (s + 1 == slots) break;
         for (int t = 1; t <= 6; ++t)  // one launch per tile count present (config batches: one)
-            if (lds_t[t]) ph_schur_launch(t, dim3(ng_max, n), sizeof(double) * (size_t)lds_t[t], stream, P);
+            if (sp.lds_u[t]) ph_schur_launch(t, sp.staged[t], ph_grid(ng_max, n), sp.bytes(t), stream, P);
         PH_CHECK("ph_schur_kernel");
         hipLaunchKernelGGL(ph_solve_kernel, dim3(n), dim3(BA_THREADS), sizeof(BaShared), stream, P);
         PH_CHECK("ph_solve_kernel");
-        if (P.imu_in_back) hipLaunchKernelGGL(ph_back_x_kernel, dim3(nch_max + 1, n), dim3(BA_THREADS), 0, stream, P);
-        else hipLaunchKernelGGL(ph_back_kernel, dim3(nch_max, n), dim3(BA_THREADS), 0, stream, P);
+        if (P.imu_in_back) hipLaunchKernelGGL(ph_back_x_kernel, ph_grid(nch_max + 1, n), dim3(BA_THREADS), 0, stream, P);
+        else hipLaunchKernelGGL(ph_back_kernel, ph_grid(nch_max, n), dim3(BA_THREADS), 0, stream, P);
         PH_CHECK("ph_back_kernel");
 
     }

@@ -68,6 +68,12 @@ int vio_layout_check(void);
  * (VIO_EINVAL outside that range). */
 int vio_ba_walk_geometry(int num_kf, int num_lm, int group_size, int32_t out[5]);
 int vio_ba_walk_div(int t, int recip);
+/* The LDS of the phase route's Schur kernel for one window shape (needs no GPU; for tests): num_kf keyframes,
+ * num_lm landmarks, `tiles` 16-row tiles of the reduced pose system (1..6), group_size landmark chunks per
+ * workgroup.  out = { dynamic LDS bytes of the launch, the kernel's static LDS bytes, 1 when the launch takes
+ * the staged instance (the group's landmark values and rhs column kept in LDS; chosen only where two
+ * workgroups per CU still fit) }. */
+int vio_ba_schur_lds(int num_kf, int num_lm, int tiles, int group_size, int32_t out[3]);
 
 /* Window-BA execution route of this context's later solves / batches (the routes give the same
    results to roundoff, each with its own fixed summation order; within a route results do not depend

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ba_global.h"
+#include "ba_launch.h"
 #include "residency.h"
 #include "ba_types.h"
 #include "ctx.h"

@@ -14,76 +14,12 @@
 #include <string>
 #include <vector>
 
+#include "ba_launch.h"
 #include "ba_types.h"
 #include "ctx.h"
 #include "residency.h"
 
 namespace vio360 {
-
-hipError_t launch_ba_windows(const BaPools& P, int n, hipStream_t stream);
-hipError_t launch_ba_pack(const BaPools& P, int n, uint8_t* dst, int64_t rec_bytes, hipStream_t stream);
-constexpr int kPhLanesMax = 4;  // sub-batches of the phase route, each on its own stream
-hipError_t launch_ba_phases(const BaPools& P, const BaWin* hw, int n, hipStream_t stream, int lanes,
-                            hipStream_t* side, hipEvent_t* ev);
-size_t ba_phase_doubles(int K, int L, int N, int T);  // sized for the smallest group (most partials)
-const char* ba_phases_failed_launch();
-hipError_t ba_phases_prepare(const BaWin* hw, int n);
-void ba_schur_lds_info(int K, int L, int T, int gs, int32_t out[3]);
-int ba_cluster_members(const BaWin* hw, int n, int max_per_window);
-hipError_t launch_ba_cluster(const BaPools& P, int n, int C, hipStream_t stream);
-hipError_t ba_cluster_prelaunch(const BaPools& P, int n, hipStream_t stream);
-bool global_ba_applicable(const vio_ba_problem& p);
-int global_ba_solve(vio_ctx* ctx, const vio_ba_problem& p, vio_ba_output* out);
-size_t ba_ws_extra_doubles();
-hipError_t launch_lie_ba(int op, const double* in, double* out, int n, hipStream_t stream);
-hipError_t launch_lie_init(int op, const double* in, double* out, int n, hipStream_t stream);
-hipError_t launch_imu_factor(const vio_preint* pre, const vio_pose* Ti, const vio_pose* Tj, const double* st,
-                             double* out, int n, hipStream_t stream);
-
-void set_error(vio_ctx* ctx, const std::string& msg) {
-    if (ctx) ctx->last_error = msg;
-}
-int hip_fail(vio_ctx* ctx, hipError_t e, const char* what) {
-    set_error(ctx, std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-    return e == hipErrorOutOfMemory ? VIO_ENOMEM : VIO_EDEVICE;
-}
-void* ctx_buffer(vio_ctx* ctx, int slot, size_t bytes) {
-    // the buffer must live on the context's device whatever device the calling thread has current
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.err != hipSuccess) return nullptr;
-    if ((int)ctx->bufs.size() <= slot) {
-        ctx->bufs.resize(slot + 1, nullptr);
-        ctx->caps.resize(slot + 1, 0);
-    }
-    if (ctx->caps[slot] >= bytes && ctx->bufs[slot]) return ctx->bufs[slot];
-    if (ctx->bufs[slot]) (void)hipFree(ctx->bufs[slot]);
-    ctx->bufs[slot] = nullptr;
-    ctx->caps[slot] = 0;
-    // 25 % headroom: per-keyframe solves grow and shrink by a few landmarks from call to call
-    size_t cap = std::max<size_t>(bytes + bytes / 4, 256);
-    if (hipMalloc(&ctx->bufs[slot], cap) != hipSuccess) return nullptr;
-    ctx->caps[slot] = cap;
-    return ctx->bufs[slot];
-}
-void* ctx_host_buffer(vio_ctx* ctx, int slot, size_t bytes) {
-    if ((int)ctx->hbufs.size() <= slot) {
-        ctx->hbufs.resize(slot + 1, nullptr);
-        ctx->hcaps.resize(slot + 1, 0);
-    }
-    if (ctx->hcaps[slot] >= bytes && ctx->hbufs[slot]) return ctx->hbufs[slot];
-    DeviceScope dev_scope(ctx->device);
-    if (dev_scope.err != hipSuccess) return nullptr;
-    if (ctx->hbufs[slot]) {
-        (void)hipStreamSynchronize(ctx->stream);  // no copy from / into the old buffer is in flight
-        (void)hipHostFree(ctx->hbufs[slot]);
-    }
-    ctx->hbufs[slot] = nullptr;
-    ctx->hcaps[slot] = 0;
-    size_t cap = std::max<size_t>(bytes + bytes / 4, 4096);
-    if (hipHostMalloc(&ctx->hbufs[slot], cap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    ctx->hcaps[slot] = cap;
-    return ctx->hbufs[slot];
-}
 
 namespace {
 
@@ -341,15 +277,39 @@ static bool env_flag(const char* name) {
     const char* e = std::getenv(name);
     return e && e[0] == '1';
 }
+static int env_int(const char* name, int unset) {
+    const char* v = std::getenv(name);
+    return v ? std::atoi(v) : unset;
+}
+// The experiment knobs (environment overrides for A/B runs and tests), read once per process.
+struct Knobs {
+    // =1: every window on the single-kernel solver / the phase route (which wins); neither takes the cluster route
+    bool monolithic = env_flag("VIO_BA_MONOLITHIC"), phases = env_flag("VIO_BA_PHASES");
+    int cluster_c = env_int("VIO_BA_CLUSTER_C", 0);  // cluster route: members per window (0: ba_cluster_members decides)
+    // IMU candidate terms beside the back-substitution walk (ph_back_x's extra workgroup) up to 64 windows
+    // (a window's serial path is then shorter: 32 windows 1.436 -> 1.342 ms, 64 windows 1.677 -> 1.633 ms,
+    // profiles/r5_imu_back_sweep.log); in ph_solve for larger batches (256 windows: 3.04 against 3.17 ms)
+    int imu_back_max = env_int("VIO_BA_IMU_BACK_MAX", 64);
+    // 0 chol6_solve2, 2 chol_tile_solve2 (where its tile geometry is instantiated, else chol6_solve2)
+    int chol = env_int("VIO_BA_CHOL", 2);
+    // sub-batches of the phase route on their own streams (launch_ba_phases), 1..kPhLanesMax
+    // (measured at 256 windows: 2 lanes 0.99x, 3 lanes 0.71x, 4 lanes 0.93x of one stream; 32 windows,
+    // 2 lanes 0.88x -- not on by default)
+    int lanes = std::max(1, std::min(kPhLanesMax, env_int("VIO_BA_LANES", 1)));
+};
+static const Knobs& knobs() {
+    static const Knobs k;
+    return k;
+}
+
 // the cluster route (one persistent launch, ba_phases.inc ph_cluster_kernel) for batches of up to
 // kClusterMaxWindows windows: a window's serial chain (prep, solve) then pays no kernel boundaries and
 // its Schur groups overlap the step control / bookkeeping; larger batches fill the chip with the phase
 // kernels
 constexpr int kClusterMaxWindows = 32;
 static bool cluster_wanted(const vio_ctx* ctx, int n) {
-    static const bool mono = env_flag("VIO_BA_MONOLITHIC"), phases = env_flag("VIO_BA_PHASES");
     if (ctx->ba_route == VIO_BA_ROUTE_CLUSTER) return true;
-    if (ctx->ba_route != VIO_BA_ROUTE_AUTO || mono || phases) return false;
+    if (ctx->ba_route != VIO_BA_ROUTE_AUTO || knobs().monolithic || knobs().phases) return false;
     return n <= kClusterMaxWindows;
 }
 
@@ -357,18 +317,20 @@ static bool cluster_wanted(const vio_ctx* ctx, int n) {
 // phase route; VIO_EDEVICE if that fails too)
 constexpr int kClusterTimeout = 1000;
 
-// Packs problems[0..n) and uploads them: descriptors, route choice, one device allocation (the batch's own,
-// or the context's grow-only arena for a one-shot solve), the input image filled on the host (a vector for
-// a reusable batch, the context's pinned staging buffer for a one-shot solve) and one host-to-device copy.
 // landmark chunks per Schur split-k group (phase route): a full config-4 shard (>= 256 windows) fills the
 // chip with 2 groups per window and halves ph_solve's partial sums; smaller batches keep more, shorter
 // groups (latency): 3 below 64 windows, 5 up to 255 (sweep of 2/3/4/5/10 at 1..256 windows,
 // profiles/r4e_gs_sweep.log); the cluster route: one chunk per group, the group's member owns its landmarks
 static int schur_group_size(int n, bool cluster) {
-    const char* gse = std::getenv("VIO_BA_SCHUR_GS");  // experiment override
+    // experiment override, not one of Knobs: read at every pack (tests/test_ba_schur_stage_gpu.py sets it
+    // between the solves of one process)
+    const char* gse = std::getenv("VIO_BA_SCHUR_GS");
     return cluster ? 1 : gse ? std::max(1, std::atoi(gse)) : n >= 256 ? 10 : n >= 64 ? 5 : 3;
 }
 
+// Packs problems[0..n) and uploads them: descriptors, route choice, one device allocation (the batch's own,
+// or the context's grow-only arena for a one-shot solve), the input image filled on the host (a vector for
+// a reusable batch, the context's pinned staging buffer for a one-shot solve) and one host-to-device copy.
 static int pack_upload(vio_ctx* ctx, BaDevice& d, const vio_ba_problem* probs, int n, bool allow_cluster) {
     Packed& pk = d.pk;
     d.n = n;
@@ -376,11 +338,8 @@ static int pack_upload(vio_ctx* ctx, BaDevice& d, const vio_ba_problem* probs, i
     std::vector<uint32_t> scratch;
     for (int i = 0; i < n; ++i)
         if (int rc = analyze_window(ctx, probs[i], pk, scratch)) return rc;
-    static const int cmax = [] {
-        const char* v = std::getenv("VIO_BA_CLUSTER_C");  // experiment override: members per window
-        return v ? std::atoi(v) : 0;
-    }();
     // (an explicitly requested cluster route takes whatever members fit: no minimum per landmark chunk)
+    const int cmax = knobs().cluster_c;
     const int cm = cmax > 0 ? cmax : ctx->ba_route == VIO_BA_ROUTE_CLUSTER ? (1 << 20) : 0;
     d.cluster_C = allow_cluster && cluster_wanted(ctx, n) ? ba_cluster_members(pk.win.data(), n, cm) : 0;
     const int gs = schur_group_size(n, d.cluster_C > 0);
@@ -459,22 +418,21 @@ static void free_batch(BaDevice& d) {
 }
 
 // the cluster route's per-window error words (a bounded hand-off wait that expired), from a host image of
-// the hand-off state
-static bool cluster_timed_out(const BaDevice& d, const int* sync) {
+// the hand-off state: kClusterTimeout, with the context's error set, when one is raised
+static int cluster_status(vio_ctx* ctx, const BaDevice& d, const int* sync) {
     for (int i = 0; i < d.n; ++i)
-        if (sync[(size_t)PH_SYNC_INTS * i + PH_SYNC_ERR]) return true;
-    return false;
+        if (sync[(size_t)PH_SYNC_INTS * i + PH_SYNC_ERR]) {
+            set_error(ctx, "cluster route: a hand-off wait timed out (workgroups not co-resident?)");
+            return kClusterTimeout;
+        }
+    return VIO_OK;
 }
 static int check_cluster(vio_ctx* ctx, BaDevice& d) {
     if (!d.cluster_C || !d.P.csync) return VIO_OK;
     std::vector<int> sync((size_t)PH_SYNC_INTS * d.n);
     VIO_HIP(ctx, hipMemcpyAsync(sync.data(), d.P.csync, sizeof(int) * sync.size(), hipMemcpyDeviceToHost, ctx->stream));
     VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (cluster_timed_out(d, sync.data())) {
-        set_error(ctx, "cluster route: a hand-off wait timed out (workgroups not co-resident?)");
-        return kClusterTimeout;
-    }
-    return VIO_OK;
+    return cluster_status(ctx, d, sync.data());
 }
 
 // Fetches the outputs region (one device-to-host copy into the context's pinned staging buffer; the cluster
@@ -490,11 +448,23 @@ static int fetch_outputs(vio_ctx* ctx, BaDevice& d, const uint8_t** img) {
     VIO_HIP(ctx, hipMemcpyAsync(h, dev + R.out_begin, R.out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *img = h - R.out_begin;  // indexable with the region offsets
-    if (d.cluster_C && cluster_timed_out(d, reinterpret_cast<const int*>(*img + R.csync))) {
-        set_error(ctx, "cluster route: a hand-off wait timed out (workgroups not co-resident?)");
-        return kClusterTimeout;
-    }
-    return VIO_OK;
+    return d.cluster_C ? cluster_status(ctx, d, reinterpret_cast<const int*>(*img + R.csync)) : VIO_OK;
+}
+
+// the summary of one window from its SI_* / SD_* words
+static void read_summary(const int32_t* si, const double* sd, vio_ba_summary& s) {
+    std::memset(&s, 0, sizeof s);
+    s.success = si[SI_SUCCESS];
+    s.termination = si[SI_TERM];
+    s.iterations = si[SI_ITERS];
+    s.num_successful_steps = si[SI_NSUCC];
+    s.num_unsuccessful_steps = si[SI_NUNSUCC];
+    s.num_inliers = si[SI_NIN];
+    s.num_outliers = si[SI_NOUT];
+    s.num_bad_lm = si[SI_NBAD];
+    s.initial_cost = sd[SD_INIT];
+    s.final_cost = sd[SD_FINAL];
+    s.fixed_cost = sd[SD_FIXED];
 }
 
 // scatters the fetched outputs into the callers' buffers (observations back in the caller's order)
@@ -530,23 +500,7 @@ static void scatter_outputs(const BaDevice& d, const uint8_t* img, vio_ba_output
             if (o.bg) std::memcpy(o.bg, ob + OL.bias, sizeof(double) * 3);
             if (o.ba) std::memcpy(o.ba, ob + OL.bias + 3, sizeof(double) * 3);
         }
-        if (o.summary) {
-            vio_ba_summary& s = *o.summary;
-            std::memset(&s, 0, sizeof s);
-            const int32_t* a = si + SI_COUNT * i;
-            const double* b = sd + SD_COUNT * i;
-            s.success = a[SI_SUCCESS];
-            s.termination = a[SI_TERM];
-            s.iterations = a[SI_ITERS];
-            s.num_successful_steps = a[SI_NSUCC];
-            s.num_unsuccessful_steps = a[SI_NUNSUCC];
-            s.num_inliers = a[SI_NIN];
-            s.num_outliers = a[SI_NOUT];
-            s.num_bad_lm = a[SI_NBAD];
-            s.initial_cost = b[SD_INIT];
-            s.final_cost = b[SD_FINAL];
-            s.fixed_cost = b[SD_FIXED];
-        }
+        if (o.summary) read_summary(si + SI_COUNT * i, sd + SD_COUNT * i, *o.summary);
         if (o.trace && o.trace_cap > 0) {
             const int n_it = std::min(std::min(si[SI_COUNT * i + SI_ITERS], w.tr_cap), o.trace_cap);
             for (int q = 0; q < n_it; ++q) o.trace[q] = tr[w.o_tr + q];
@@ -561,49 +515,45 @@ static int download_batch(vio_ctx* ctx, BaDevice& d, vio_ba_output* outs) {
     return VIO_OK;
 }
 
-// LocalBA / BA / VIBA windows run as the phase-kernel sequence (ba_phases.inc): a window's
-// observation walks spread over many workgroups per phase, so it is the faster route at every batch
-// size measured (1 window: 1.42 vs 1.70 ms; the 256-window config-4 shard: 3.59 vs 3.75 ms per 10
-// iterations).  PnP windows (outlier rounds inside one solve) run in ba_window_kernel, the
-// single-kernel solver.  Within a route a window's result does not depend on the batch it is in.
-// vio_ctx_set_ba_route / VIO_BA_MONOLITHIC=1 / VIO_BA_PHASES=1 select a route explicitly (A/B runs,
-// tests); per-window phase profiling runs on ba_window_kernel.
-static bool force_monolithic(const vio_ctx* ctx, const BaDevice& d) {
-    static const bool mono = env_flag("VIO_BA_MONOLITHIC"), phases = env_flag("VIO_BA_PHASES");
-    if (phases || ctx->ba_route == VIO_BA_ROUTE_PHASES) return false;
-    return mono || d.P.prof || ctx->ba_route == VIO_BA_ROUTE_SINGLE_KERNEL;
+// The route of a batch's LocalBA / BA / VIBA windows (VIO_BA_ROUTE_SINGLE_KERNEL / _PHASES / _CLUSTER).  They
+// run as the phase-kernel sequence (ba_phases.inc): a window's observation walks spread over many
+// workgroups per phase, so it is the faster route at every batch size measured (1 window: 1.42 vs 1.70 ms;
+// the 256-window config-4 shard: 3.59 vs 3.75 ms per 10 iterations).  PnP windows (outlier rounds inside
+// one solve) run in ba_window_kernel, the single-kernel solver, whatever the route.  Within a route a
+// window's result does not depend on the batch it is in.  vio_ctx_set_ba_route / VIO_BA_MONOLITHIC=1 /
+// VIO_BA_PHASES=1 select a route explicitly (A/B runs, tests); per-window phase profiling runs on
+// ba_window_kernel.  The cluster route is fixed at pack time (d.cluster_C, cluster_wanted); phases against
+// the single kernel is decided at every launch, from d.P.prof and the context's route at that moment.
+static int batch_route(const vio_ctx* ctx, const BaDevice& d) {
+    bool any_other = false;
+    for (const BaWin& w : d.pk.win) any_other |= !w.is_pnp;
+    if (!any_other) return VIO_BA_ROUTE_SINGLE_KERNEL;
+    if (d.cluster_C > 0) return VIO_BA_ROUTE_CLUSTER;
+    if (knobs().phases || ctx->ba_route == VIO_BA_ROUTE_PHASES) return VIO_BA_ROUTE_PHASES;
+    return knobs().monolithic || d.P.prof || ctx->ba_route == VIO_BA_ROUTE_SINGLE_KERNEL ? VIO_BA_ROUTE_SINGLE_KERNEL
+                                                                                          : VIO_BA_ROUTE_PHASES;
 }
 
-static int launch(vio_ctx* ctx, BaDevice& d, bool timed) {
-    VIO_DEVICE(ctx);
-    if (timed) VIO_HIP(ctx, hipEventRecord(d.ev0, ctx->stream));
-    bool any_pnp = false, any_other = false;
-    for (const BaWin& w : d.pk.win) (w.is_pnp ? any_pnp : any_other) = true;
-    const bool cluster = any_other && d.cluster_C > 0;
-    const bool phases = !cluster && any_other && !force_monolithic(ctx, d);
-    d.P.route = phases || cluster ? 1 : 0;
-    // IMU candidate terms beside the back-substitution walk (ph_back_x's extra workgroup) up to 64 windows
-    // (a window's serial path is then shorter: 32 windows 1.436 -> 1.342 ms, 64 windows 1.677 -> 1.633 ms,
-    // profiles/r5_imu_back_sweep.log); in ph_solve for larger batches (256 windows: 3.04 against 3.17 ms)
-    static const int imu_back_max = [] {
-        const char* v = std::getenv("VIO_BA_IMU_BACK_MAX");  // experiment override
-        return v ? std::atoi(v) : 64;
-    }();
-    d.P.imu_in_back = cluster || d.n <= imu_back_max ? 1 : 0;  // cluster: the leader, beside the walks
-    static const int chol_variant = [] {
-        const char* v = std::getenv("VIO_BA_CHOL");  // experiment override: 0 chol6_solve2, 2 chol_tile_solve2
-        return v ? std::atoi(v) : 2;  // (chol_tile_solve2 where its tile geometry is instantiated, else chol6_solve2)
-    }();
-    d.P.chol_variant = chol_variant;
-    d.P.win_base = 0;
-    // sub-batches of the phase route on their own streams (launch_ba_phases): large batches only
-    static const int lanes_env = [] {
-        const char* v = std::getenv("VIO_BA_LANES");  // experiment override
-        return v ? std::max(1, std::min(kPhLanesMax, std::atoi(v))) : 0;
-    }();
-    // (measured at 256 windows: 2 lanes 0.99x, 3 lanes 0.71x, 4 lanes 0.93x of one stream; 32 windows,
-    // 2 lanes 0.88x -- not on by default)
-    int lanes = lanes_env ? lanes_env : 1;
+// Captures what `enqueue` puts on the context's stream into d.phase_graph.  A failed launch inside the
+// capture wins over the end-capture status.
+template <class Enqueue>
+static hipError_t capture_graph(vio_ctx* ctx, BaDevice& d, Enqueue enqueue) {
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        const hipError_t el = enqueue();
+        e = hipStreamEndCapture(ctx->stream, &g);
+        if (el != hipSuccess) e = el;
+    }
+    if (e == hipSuccess) e = hipGraphInstantiate(&d.phase_graph, g, nullptr, nullptr, 0);
+    if (g) (void)hipGraphDestroy(g);
+    return e;
+}
+
+// the side streams and fork / join events of the phase route's sub-batches, created on first use: the lane
+// count, fewer than asked for when a create fails
+static int ensure_lanes(BaDevice& d) {
+    int lanes = knobs().lanes;
     for (int l = 0; l < lanes; ++l) {
         if (l > 0 && !d.lane_st[l - 1] && hipStreamCreateWithFlags(&d.lane_st[l - 1], hipStreamNonBlocking) != hipSuccess) {
             d.lane_st[l - 1] = nullptr;
@@ -616,59 +566,86 @@ static int launch(vio_ctx* ctx, BaDevice& d, bool timed) {
             break;
         }
     }
+    return lanes;
+}
+
+// the fields of BaPools that a run sets
+static void set_run_fields(BaDevice& d, int route) {
+    d.P.route = route == VIO_BA_ROUTE_SINGLE_KERNEL ? 0 : 1;
+    d.P.imu_in_back = route == VIO_BA_ROUTE_CLUSTER || d.n <= knobs().imu_back_max ? 1 : 0;  // cluster: the leader, beside the walks
+    d.P.chol_variant = knobs().chol;
+    d.P.win_base = 0;
+}
+
+static hipError_t run_cluster(vio_ctx* ctx, BaDevice& d) {
+    hipError_t e = hipSuccess;
+    if (d.reusable && !d.phase_graph)  // the kernel alone is captured; its hand-off words are cleared per run
+        e = capture_graph(ctx, d, [&] { return launch_ba_cluster(d.P, d.n, d.cluster_C, ctx->stream); });
+    if (e == hipSuccess) e = ba_cluster_prelaunch(d.P, d.n, ctx->stream);
+    if (e != hipSuccess) return e;
+    // every member of every window resident at once, also beside other threads' persistent launches
+    ResidencyGuard rg(ctx->stream, d.cluster_C * d.n);
+    e = rg.status();
+    if (e == hipSuccess) e = d.reusable ? hipGraphLaunch(d.phase_graph, ctx->stream)
+                                        : launch_ba_cluster(d.P, d.n, d.cluster_C, ctx->stream);
+    if (e == hipSuccess) e = rg.commit();
+    return e;
+}
+
+// ~70 launches per solve: a reusable batch captures them once into a graph (same arguments every run) and
+// replays it; a one-shot solve launches them directly.  `what` names the call that failed.
+static hipError_t run_phases(vio_ctx* ctx, BaDevice& d, const char*& what) {
+    hipError_t e = ba_phases_prepare(d.pk.win.data(), d.n);
+    if (e != hipSuccess) {
+        what = "hipFuncSetAttribute(phase kernels)";
+        return e;
+    }
+    const int lanes = ensure_lanes(d);
+    auto enqueue = [&] {
+        const hipError_t el = launch_ba_phases(d.P, d.pk.win.data(), d.n, ctx->stream, lanes, d.lane_st, d.lane_ev);
+        if (el != hipSuccess) what = ba_phases_failed_launch();
+        return el;
+    };
+    if (!d.reusable) return enqueue();
+    if (!d.phase_graph) e = capture_graph(ctx, d, enqueue);
+    return e == hipSuccess ? hipGraphLaunch(d.phase_graph, ctx->stream) : e;
+}
+
+static int launch(vio_ctx* ctx, BaDevice& d, bool timed) {
+    VIO_DEVICE(ctx);
+    if (timed) VIO_HIP(ctx, hipEventRecord(d.ev0, ctx->stream));
+    const int route = batch_route(ctx, d);
+    set_run_fields(d, route);
     hipError_t e = hipSuccess;
     const char* what = "ba_window_kernel launch";
-    if (cluster) {
+    if (route == VIO_BA_ROUTE_CLUSTER) {
         what = "ph_cluster_kernel";
-        if (d.reusable && !d.phase_graph) {  // the kernel alone is captured; its hand-off words are cleared per run
-            hipGraph_t g = nullptr;
-            e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                hipError_t el = launch_ba_cluster(d.P, d.n, d.cluster_C, ctx->stream);
-                e = hipStreamEndCapture(ctx->stream, &g);
-                if (el != hipSuccess) e = el;
-            }
-            if (e == hipSuccess) e = hipGraphInstantiate(&d.phase_graph, g, nullptr, nullptr, 0);
-            if (g) (void)hipGraphDestroy(g);
-        }
-        if (e == hipSuccess) e = ba_cluster_prelaunch(d.P, d.n, ctx->stream);
-        if (e == hipSuccess) {
-            // every member of every window resident at once, also beside other threads' persistent launches
-            ResidencyGuard rg(ctx->stream, d.cluster_C * d.n);
-            e = rg.status();
-            if (e == hipSuccess) e = d.reusable ? hipGraphLaunch(d.phase_graph, ctx->stream)
-                                                : launch_ba_cluster(d.P, d.n, d.cluster_C, ctx->stream);
-            if (e == hipSuccess) e = rg.commit();
-        }
-    } else if (phases) {
-        // ~70 launches per solve: a reusable batch captures them once into a graph (same arguments
-        // every run) and replays it; a one-shot solve launches them directly
-        e = ba_phases_prepare(d.pk.win.data(), d.n);
-        if (e != hipSuccess) what = "hipFuncSetAttribute(phase kernels)";
-        if (e == hipSuccess && !d.reusable) {
-            e = launch_ba_phases(d.P, d.pk.win.data(), d.n, ctx->stream, lanes, d.lane_st, d.lane_ev);
-            if (e != hipSuccess) what = ba_phases_failed_launch();
-        } else if (e == hipSuccess && !d.phase_graph) {
-            hipGraph_t g = nullptr;
-            e = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                hipError_t el = launch_ba_phases(d.P, d.pk.win.data(), d.n, ctx->stream, lanes, d.lane_st, d.lane_ev);
-                e = hipStreamEndCapture(ctx->stream, &g);
-                if (el != hipSuccess) e = el, what = ba_phases_failed_launch();
-            }
-            if (e == hipSuccess) e = hipGraphInstantiate(&d.phase_graph, g, nullptr, nullptr, 0);
-            if (g) (void)hipGraphDestroy(g);
-        }
-        if (e == hipSuccess && d.reusable) e = hipGraphLaunch(d.phase_graph, ctx->stream);
+        e = run_cluster(ctx, d);
+    } else if (route == VIO_BA_ROUTE_PHASES) {
+        e = run_phases(ctx, d, what);
     }
     // the single-kernel solver: PnP windows, or every window when neither batched route runs (the cluster
     // route has no window for it otherwise: an empty launch would cost the batch a kernel boundary)
-    if (e == hipSuccess && (any_pnp || (!phases && !cluster))) e = launch_ba_windows(d.P, d.n, ctx->stream);
+    bool any_pnp = false;
+    for (const BaWin& w : d.pk.win) any_pnp |= w.is_pnp != 0;
+    if (e == hipSuccess && (any_pnp || route == VIO_BA_ROUTE_SINGLE_KERNEL)) e = launch_ba_windows(d.P, d.n, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, what);
     if (timed) {
         VIO_HIP(ctx, hipEventRecord(d.ev1, ctx->stream));
         d.timing_pending = true;
     }
+    return VIO_OK;
+}
+
+// folds a pending start / end event pair of a timed run into the batch's kernel-time sum
+static int fold_timing(vio_ctx* ctx, BaDevice& d) {
+    if (!d.timing_pending) return VIO_OK;
+    VIO_HIP(ctx, hipEventSynchronize(d.ev1));
+    float ms = 0.f;
+    VIO_HIP(ctx, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    d.ms_sum += ms;
+    d.ms_count++;
+    d.timing_pending = false;
     return VIO_OK;
 }
 
@@ -714,81 +691,6 @@ struct vio_ba_batch {
 
 extern "C" {
 
-int vio_abi_version(void) { return VIO360_ABI_VERSION; }
-
-int vio_ctx_set_ba_route(vio_ctx* ctx, int route) {
-    if (!ctx || route < VIO_BA_ROUTE_AUTO || route > VIO_BA_ROUTE_CLUSTER) return VIO_EINVAL;
-    ctx->ba_route = route;
-    return VIO_OK;
-}
-
-int vio_lie_eval(vio_ctx* ctx, int op, const double* in, int n, double* out) {
-    static const int kIn[5] = {3, 6, 9, 3, 9}, kOut[5] = {9, 12, 3, 9, 3};
-    if (!ctx || op < VIO_LIE_SO3_EXP || op > VIO_LIE_SO3D_LOG || n < 0 || (n > 0 && (!in || !out))) return VIO_EINVAL;
-    if (n == 0) return VIO_OK;
-    const size_t bi = sizeof(double) * kIn[op] * (size_t)n, bo = sizeof(double) * kOut[op] * (size_t)n;
-    auto* d = static_cast<char*>(ctx_buffer(ctx, kSlotLie, bi + bo));
-    if (!d) {
-        set_error(ctx, "vio_lie_eval: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    VIO_DEVICE(ctx);
-    double* din = reinterpret_cast<double*>(d);
-    double* dout = reinterpret_cast<double*>(d + bi);
-    VIO_HIP(ctx, hipMemcpyAsync(din, in, bi, hipMemcpyHostToDevice, ctx->stream));
-    VIO_HIP(ctx, op <= VIO_LIE_IMU_LOG ? launch_lie_ba(op, din, dout, n, ctx->stream)
-                                       : launch_lie_init(op, din, dout, n, ctx->stream));
-    VIO_HIP(ctx, hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, ctx->stream));
-    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VIO_OK;
-}
-
-int vio_imu_factor_eval(vio_ctx* ctx, int n, const vio_preint* preint, const double* gravity, const vio_pose* T_wb_i_init,
-                        const vio_pose* T_wb_j_init, const double* delta_i, const double* v_i, const double* bg,
-                        const double* ba, const double* delta_j, const double* v_j, double* out) {
-    constexpr size_t kIn = 27, kOut = 315;
-    if (!ctx || n < 0) return VIO_EINVAL;
-    if (n > 0 && (!preint || !gravity || !T_wb_i_init || !T_wb_j_init || !delta_i || !v_i || !bg || !ba || !delta_j ||
-                  !v_j || !out))
-        return VIO_EINVAL;
-    if (n == 0) return VIO_OK;
-    const size_t N = (size_t)n, b_pre = sizeof(vio_preint) * N, b_pose = sizeof(vio_pose) * N,
-                 b_st = sizeof(double) * kIn * N, b_in = b_pre + 2 * b_pose + b_st, b_out = sizeof(double) * kOut * N;
-    static_assert(sizeof(vio_preint) % 8 == 0 && sizeof(vio_pose) % 8 == 0, "the packed inputs stay 8-byte aligned");
-    auto* d = static_cast<char*>(ctx_buffer(ctx, kSlotLie, b_in + b_out));
-    if (!d) {
-        set_error(ctx, "vio_imu_factor_eval: device allocation failed");
-        return VIO_ENOMEM;
-    }
-    std::vector<char> h(b_in);
-    std::memcpy(h.data(), preint, b_pre);
-    std::memcpy(h.data() + b_pre, T_wb_i_init, b_pose);
-    std::memcpy(h.data() + b_pre + b_pose, T_wb_j_init, b_pose);
-    double* st = reinterpret_cast<double*>(h.data() + b_pre + 2 * b_pose);
-    for (size_t f = 0; f < N; ++f) {
-        double* s = st + kIn * f;
-        std::memcpy(s, gravity + 3 * f, sizeof(double) * 3);
-        std::memcpy(s + 3, delta_i + 6 * f, sizeof(double) * 6);
-        std::memcpy(s + 9, v_i + 3 * f, sizeof(double) * 3);
-        std::memcpy(s + 12, bg + 3 * f, sizeof(double) * 3);
-        std::memcpy(s + 15, ba + 3 * f, sizeof(double) * 3);
-        std::memcpy(s + 18, delta_j + 6 * f, sizeof(double) * 6);
-        std::memcpy(s + 24, v_j + 3 * f, sizeof(double) * 3);
-    }
-    VIO_DEVICE(ctx);
-    VIO_HIP(ctx, hipMemcpyAsync(d, h.data(), b_in, hipMemcpyHostToDevice, ctx->stream));
-    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (h is pageable: the copy has left it)
-    VIO_HIP(ctx, launch_imu_factor(reinterpret_cast<const vio_preint*>(d), reinterpret_cast<const vio_pose*>(d + b_pre),
-                                   reinterpret_cast<const vio_pose*>(d + b_pre + b_pose),
-                                   reinterpret_cast<const double*>(d + b_pre + 2 * b_pose),
-                                   reinterpret_cast<double*>(d + b_in), n, ctx->stream));
-    VIO_HIP(ctx, hipMemcpyAsync(out, d + b_in, b_out, hipMemcpyDeviceToHost, ctx->stream));
-    VIO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VIO_OK;
-}
-
-static std::string g_create_error;
-
 int vio_layout_check(void) {
     const uint64_t ba = ba_layout_sig(), gba = gba_layout_sig_ba_global();
     return ba == ba_layout_sig_ba_kernel() && ba == ba_layout_sig_ba_cluster() && ba == ba_layout_sig_ba_global_host() &&
@@ -820,58 +722,6 @@ int vio_ba_walk_div(int t, int recip) {
     return walk_div(t, recip);
 }
 
-int vio_ctx_create(int device, vio_ctx** out) {
-    if (!out) return VIO_EINVAL;
-    *out = nullptr;
-    if (vio_layout_check() != VIO_OK) {
-        g_create_error = "translation units disagree on the BaWin/BaPools/GbaArgs layout (stale object: rebuild)";
-        return VIO_EDEVICE;
-    }
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        g_create_error = "no HIP device available";
-        return VIO_EDEVICE;
-    }
-    if (device < 0 || device >= n) {
-        g_create_error = "device index out of range";
-        return VIO_EINVAL;
-    }
-    DeviceScope dev_scope(device);
-    if (dev_scope.err != hipSuccess) {
-        g_create_error = "hipSetDevice failed";
-        return VIO_EDEVICE;
-    }
-    vio_ctx* c = new vio_ctx();
-    c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        g_create_error = "hipStreamCreate failed";
-        return VIO_EDEVICE;
-    }
-    *out = c;
-    return VIO_OK;
-}
-
-void vio_ctx_destroy(vio_ctx* ctx) {
-    if (!ctx) return;
-    DeviceScope _vio_dev_scope(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->gba_cache.reset();  // its graph / side stream before the buffers and the stream
-    for (void* p : ctx->bufs)
-        if (p) (void)hipFree(p);
-    for (void* p : ctx->hbufs)
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
-
-const char* vio_ctx_last_error(const vio_ctx* ctx) {
-    return ctx ? ctx->last_error.c_str() : g_create_error.c_str();
-}
-
 int vio_ba_batch_create(vio_ctx* ctx, const vio_ba_problem* probs, int n, vio_ba_batch** out) {
     if (!ctx || !probs || n <= 0 || !out) return VIO_EINVAL;
     *out = nullptr;
@@ -894,14 +744,7 @@ int vio_ba_batch_run(vio_ba_batch* b) {
     if (!b) return VIO_EINVAL;
     vio_ctx* ctx = b->ctx;
     VIO_DEVICE(ctx);
-    if (b->dev.timing_pending) {  // fold the previous run's time in before re-recording
-        VIO_HIP(ctx, hipEventSynchronize(b->dev.ev1));
-        float ms = 0.f;
-        VIO_HIP(ctx, hipEventElapsedTime(&ms, b->dev.ev0, b->dev.ev1));
-        b->dev.ms_sum += ms;
-        b->dev.ms_count++;
-        b->dev.timing_pending = false;
-    }
+    if (int rc = fold_timing(ctx, b->dev)) return rc;  // the previous run's time, before re-recording
     return launch(ctx, b->dev, true);
 }
 
@@ -946,14 +789,7 @@ int vio_ba_batch_download(vio_ba_batch* b, vio_ba_output* outs) {
 int vio_ba_batch_kernel_ms(vio_ba_batch* b, double* avg_ms, int* count) {
     if (!b || !avg_ms || !count) return VIO_EINVAL;
     VIO_DEVICE(b->ctx);
-    if (b->dev.timing_pending) {
-        VIO_HIP(b->ctx, hipEventSynchronize(b->dev.ev1));
-        float ms = 0.f;
-        VIO_HIP(b->ctx, hipEventElapsedTime(&ms, b->dev.ev0, b->dev.ev1));
-        b->dev.ms_sum += ms;
-        b->dev.ms_count++;
-        b->dev.timing_pending = false;
-    }
+    if (int rc = fold_timing(b->ctx, b->dev)) return rc;
     *count = b->dev.ms_count;
     *avg_ms = b->dev.ms_count ? b->dev.ms_sum / b->dev.ms_count : 0.0;
     b->dev.ms_sum = 0.0;
@@ -963,11 +799,7 @@ int vio_ba_batch_kernel_ms(vio_ba_batch* b, double* avg_ms, int* count) {
 
 int vio_ba_batch_route(vio_ba_batch* b, int* route, int* workgroups_per_window) {
     if (!b || !route) return VIO_EINVAL;
-    bool any_other = false;
-    for (const BaWin& w : b->dev.pk.win) any_other |= !w.is_pnp;
-    *route = any_other && b->dev.cluster_C > 0 ? VIO_BA_ROUTE_CLUSTER
-             : any_other && !force_monolithic(b->ctx, b->dev) ? VIO_BA_ROUTE_PHASES
-                                                                : VIO_BA_ROUTE_SINGLE_KERNEL;
+    *route = batch_route(b->ctx, b->dev);
     if (workgroups_per_window) *workgroups_per_window = b->dev.cluster_C;
     return VIO_OK;
 }
@@ -1068,19 +900,7 @@ int vio_ba_record_unpack(const void* record, size_t record_bytes, vio_ba_output*
         double d[SD_COUNT];
         std::memcpy(a, rec + R.si, sizeof a);
         std::memcpy(d, rec + R.sd, sizeof d);
-        vio_ba_summary& s = *out->summary;
-        std::memset(&s, 0, sizeof s);
-        s.success = a[SI_SUCCESS];
-        s.termination = a[SI_TERM];
-        s.iterations = a[SI_ITERS];
-        s.num_successful_steps = a[SI_NSUCC];
-        s.num_unsuccessful_steps = a[SI_NUNSUCC];
-        s.num_inliers = a[SI_NIN];
-        s.num_outliers = a[SI_NOUT];
-        s.num_bad_lm = a[SI_NBAD];
-        s.initial_cost = d[SD_INIT];
-        s.final_cost = d[SD_FINAL];
-        s.fixed_cost = d[SD_FIXED];
+        read_summary(a, d, *out->summary);
     }
     return VIO_OK;
 }

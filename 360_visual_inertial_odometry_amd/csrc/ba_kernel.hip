@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "ba_types.h"
+#include "ba_launch.h"
 #include "ba_global.h"
 #include "ba_factor_dev.h"
 #include "chol_dev.h"

@@ -4,7 +4,6 @@
 
 #include <memory>
 #include <string>
-#include <vector>
 
 #include "vio360.h"
 
@@ -12,16 +11,52 @@
 // histograms done / LUTs done / end)
 enum { kEvImu = 0, kEvTri = 2, kEvResize = 4, kEvInit = 6, kEvEq = 8, kEvMask = 12, kEvCount = 14 };
 
+// Device scratch slots of vio_ctx::bufs (ctx_buffer), one owner each.
+enum {
+    // vio_imu_preintegrate
+    kSlotImuData, kSlotImuIntervals, kSlotImuOut,
+    // vio_triangulate
+    kSlotTriIn, kSlotTriOut,
+    // the frame resize and ingest (resize_host.cpp): the host entry points' source and result (every
+    // preprocessing stage stages its source in kSlotResizeSrc), the general path's per-output-column /
+    // per-output-row tap tables, and the two-pass ingest route's grey camera-resolution plane between the
+    // convert and the resize
+    kSlotResizeSrc, kSlotResizeDst, kSlotResizeTabX, kSlotResizeTabY, kSlotIngestPlane,
+    // erp_tracker_upload_warped: the warped frame of the supersampled route, before the resize
+    kSlotWarpDst,
+    // staging of vio_ba_batch_pack to host memory
+    kSlotRecords,
+    // vio_imu_init_solve inputs, outputs and per-problem scratch
+    kSlotImuInit,
+    // vio_mono_init_solve inputs, outputs and scratch
+    kSlotMonoInit,
+    // vio_lie_eval / vio_imu_factor_eval inputs and outputs
+    kSlotLie,
+    // the one-shot window solves' arena (vio_ba_solve[_batched]: inputs, outputs, workspace)
+    kSlotBaSolve,
+    // the global BA solves' arena (inputs, outputs, the dense reduced system and the rest of the state)
+    kSlotGbaSolve,
+    // erp_equalize*: per-workgroup partial histograms, the tiles' LUTs, and the host entry point's frame
+    kSlotEqHist, kSlotEqLut, kSlotEqSrc, kSlotEqDst,
+    // the region-mask builds (mask_host.cpp): the uploaded host mask, the two intermediate planes, the
+    // footprint tables, the 0 / 255 image of the host entry points
+    kSlotMaskSrc, kSlotMaskTmp0, kSlotMaskTmp1, kSlotMaskTab, kSlotMaskDst,
+    kSlotCount
+};
+// Pinned host slots of vio_ctx::hbufs (ctx_host_buffer): the one-shot window solves' input image, every BA
+// download's outputs image, the global BA solves' staging
+enum { kHostSlotBaIn, kHostSlotBaOut, kHostSlotGba, kHostSlotCount };
+
 struct vio_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string last_error;
     // grow-only device buffers keyed by slot
-    std::vector<void*> bufs;
-    std::vector<size_t> caps;
+    void* bufs[kSlotCount] = {};
+    size_t caps[kSlotCount] = {};
     // grow-only pinned host staging buffers keyed by slot
-    std::vector<void*> hbufs;
-    std::vector<size_t> hcaps;
+    void* hbufs[kHostSlotCount] = {};
+    size_t hcaps[kHostSlotCount] = {};
     // kernel timing of every module: the events of kEv* (created on first use, frame_io.h events_ready)
     hipEvent_t ev[kEvCount] = {};
     float imu_ms = -1.f;  // < 0: no IMU preintegration has run on this context
@@ -49,29 +84,6 @@ int hip_fail(vio_ctx* ctx, hipError_t e, const char* what);
 void* ctx_buffer(vio_ctx* ctx, int slot, size_t bytes);
 // pinned host buffer of at least `bytes` for slot `slot` (contents undefined); nullptr on failure
 void* ctx_host_buffer(vio_ctx* ctx, int slot, size_t bytes);
-// scratch slots owned by vio_imu_preintegrate
-enum { kSlotImuData = 8, kSlotImuIntervals = 9, kSlotImuOut = 10 };
-// scratch slots owned by vio_triangulate
-enum { kSlotTriIn = 11, kSlotTriOut = 12 };
-// (slots 13, 14 and 21 to 23: the frame resize and ingest, resize.h)
-// staging of vio_ba_batch_pack to host memory
-enum { kSlotRecords = 15 };
-// vio_imu_init_solve inputs, outputs and per-problem scratch
-enum { kSlotImuInit = 16 };
-// vio_mono_init_solve inputs, outputs and scratch
-enum { kSlotMonoInit = 17 };
-// vio_lie_eval inputs and outputs
-enum { kSlotLie = 18 };
-// the one-shot window solves' arena (vio_ba_solve[_batched]: inputs, outputs, workspace)
-enum { kSlotBaSolve = 19 };
-// the global BA solves' arena (inputs, outputs, the dense reduced system and the rest of the state)
-enum { kSlotGbaSolve = 20 };
-// erp_equalize*: per-workgroup partial histograms, the tiles' LUTs, and the host entry point's frame
-enum { kSlotEqHist = 25, kSlotEqLut = 26, kSlotEqSrc = 27, kSlotEqDst = 28 };
-// (slots 29 to 33: the region-mask builds, mask.h)
-// pinned host slots: the one-shot solves' input image and every BA download's outputs image
-enum { kHostSlotBaIn = 0, kHostSlotBaOut = 1, kHostSlotGba = 2 };
-
 // Selects a device for the rest of the enclosing scope and restores the calling thread's current
 // device on exit, so a C-ABI call never leaves the caller's thread on the context's device (a process
 // that also drives other GPUs, e.g. through torch, keeps its own current device).

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ba_launch.h"
 #include "ctx.h"
 #include "lie_dev.h"
 #include "vio360.h"

@@ -67,8 +67,4 @@ int mask_warp_check(const erp_warp* w, const uint8_t* src_mask, int stride, int 
 // a host mask (W x H u8) into the context's device copy, rows padded to 16 bytes; errors carry `who`
 int mask_stage(vio_ctx* ctx, const uint8_t* mask, int W, int H, int stride, const char* who, uint8_t** d, int* pitch);
 
-// scratch slots of the mask builds: the uploaded host mask, the two intermediate planes, the footprint tables, the
-// 0 / 255 image of the host entry points
-enum { kSlotMaskSrc = 29, kSlotMaskTmp0 = 30, kSlotMaskTmp1 = 31, kSlotMaskTab = 32, kSlotMaskDst = 33 };
-
 }  // namespace vio360

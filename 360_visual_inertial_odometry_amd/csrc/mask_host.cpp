@@ -56,8 +56,7 @@ bool footprints(int ssize, int dsize, int32_t* out) {
 int footprint_tables(vio_ctx* ctx, int sW, int dW, int sH, int dH, const int32_t** fx, const int32_t** fy) {
     const int key[4] = {sW, dW, sH, dH};
     const size_t bytes = sizeof(int32_t) * 2 * ((size_t)dW + dH);
-    const bool hit = !std::memcmp(key, ctx->mask_tab_key, sizeof key) && (int)ctx->bufs.size() > kSlotMaskTab &&
-                     ctx->bufs[kSlotMaskTab];
+    const bool hit = !std::memcmp(key, ctx->mask_tab_key, sizeof key) && ctx->bufs[kSlotMaskTab];
     if (!hit) {
         std::vector<int32_t> tab(2 * ((size_t)dW + dH));
         if (!footprints(sW, dW, tab.data()) || !footprints(sH, dH, tab.data() + 2 * (size_t)dW)) {

@@ -50,9 +50,4 @@ hipError_t launch_area_general(const ResizeAnyArgs& a, int mode, int dH, int n_f
 // packed -> pitched u8 plane of the same size (mode: kPixByte, kPixBytes3 or kPixDword)
 hipError_t launch_ingest_convert(const ResizeArgs& a, int mode, int n_frames, hipStream_t stream);
 
-// scratch slots: the host entry points' source and result (every preprocessing stage stages its source in
-// kSlotResizeSrc), the general path's per-output-column / per-output-row tap tables, and the two-pass ingest
-// route's grey camera-resolution plane between the convert and the resize
-enum { kSlotResizeSrc = 13, kSlotResizeDst = 14, kSlotResizeTabX = 21, kSlotResizeTabY = 22, kSlotIngestPlane = 23 };
-
 }  // namespace vio360

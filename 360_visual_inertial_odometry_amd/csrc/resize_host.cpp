@@ -72,8 +72,8 @@ bool area_tab_compact(const std::vector<AreaTap>& tab, int ssize, int dsize, std
 int general_tables(vio_ctx* ctx, int W, int dW, int H, int dH, const AreaTaps** d_tx, const AreaTaps** d_ty,
                    int* max_x_taps) {
     const int key[4] = {W, dW, H, dH};
-    const bool hit = !std::memcmp(key, ctx->rsz_tab_key, sizeof(key)) && (int)ctx->bufs.size() > kSlotResizeTabY &&
-                     ctx->bufs[kSlotResizeTabX] && ctx->bufs[kSlotResizeTabY];
+    const bool hit = !std::memcmp(key, ctx->rsz_tab_key, sizeof(key)) && ctx->bufs[kSlotResizeTabX] &&
+                     ctx->bufs[kSlotResizeTabY];
     if (!hit) {
         std::memset(ctx->rsz_tab_key, 0, sizeof(key));
         std::vector<AreaTap> tab;

@@ -43,7 +43,4 @@ struct WarpArgs {
 // holds bit shifts, kPixDword stands for 4-byte pixels at any alignment and kPixBytes3 for 3-byte pixels.
 hipError_t launch_warp(const WarpArgs& a, int mode, bool pair, hipStream_t stream);
 
-// scratch slot of erp_tracker_upload_warped: the warped frame of the supersampled route, before the resize
-enum { kSlotWarpDst = 24 };
-
 }  // namespace vio360

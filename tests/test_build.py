@@ -47,6 +47,9 @@ def built(vio):
     ("resize.h", {"resize", "resize_host"}),
     ("frame_io.h", {"resize_host", "warp_host", "equalize_host", "mask_host", "tracker_host"}),
     ("tracker_types.h", {"tracker", "tracker_host", "frontend_host"}),
+    # (new rows go last: the generated ids of the rows above carry their position)
+    ("ba_launch.h", {"ba_kernel", "ba_cluster", "ba_host", "ba_global_host", "imu_init", "lie_host"}),
+    ("ctx.h", {"ctx", "ba_host", "ba_global_host", "tracker_host", "resize_host"}),
 ])
 def test_touching_a_header_rebuilds_its_dependents(built, header, must):
     deps = set(_includers(header))

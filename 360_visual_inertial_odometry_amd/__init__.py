@@ -63,6 +63,8 @@ EXPORTS = [
     "erp_tracker_set_mask", "erp_tracker_set_mask_device", "erp_tracker_set_mask_warped", "erp_tracker_get_mask",
     "erp_frontend_set_mask", "erp_frontend_set_mask_device", "erp_frontend_set_mask_warped",
     "erp_seam_check", "erp_klt_track_seam", "erp_gftt_seam", "erp_tracker_set_seam", "erp_frontend_set_seam",
+    "erp_klt_track_guess", "erp_klt_track_rot", "erp_tracker_set_guess", "erp_tracker_set_rotation",
+    "erp_tracker_download_guess", "erp_frontend_predict_rotation", "erp_predict_from_preint",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -204,6 +206,16 @@ def lib():
         L.erp_gftt_seam.argtypes = L.erp_gftt.argtypes + [C.c_int]
         L.erp_tracker_set_seam.argtypes = [vp, C.c_int]
         L.erp_frontend_set_seam.argtypes = [vp, C.c_int]
+    if hasattr(L, "erp_klt_track_guess") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        L.erp_klt_track_guess.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                          C.POINTER(abi.ErpKltParams), C.c_int]
+        L.erp_klt_track_rot.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp,
+                                        C.POINTER(abi.ErpKltParams), C.c_int]
+        L.erp_tracker_set_guess.argtypes = [vp, vp, C.c_int]
+        L.erp_tracker_set_rotation.argtypes = [vp, vp]
+        L.erp_tracker_download_guess.argtypes = [vp, vp]
+        L.erp_frontend_predict_rotation.argtypes = [vp, vp]
+        L.erp_predict_from_preint.argtypes = [C.POINTER(abi.VioPreint), vp, vp]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -539,9 +551,12 @@ class Context:
         return _kernel_ms(self, self.h, "erp_resize_area_kernel_ms")
 
     # ---- ERP feature tracking ----
-    def klt_track(self, prev, curr, pts, params=None, seam=None):
+    def klt_track(self, prev, curr, pts, params=None, seam=None, guess=None, rot=None):
         """cv::calcOpticalFlowPyrLK as FeatureTracker::TrackOpticalFlow calls it -> (next, status, err).
-        seam (VIO_SEAM_*): erp_klt_track_seam; VIO_SEAM_WRAP tracks across the ERP seam, next.x in [0, W)."""
+        seam (VIO_SEAM_*): erp_klt_track_seam; VIO_SEAM_WRAP tracks across the ERP seam, next.x in [0, W).
+        guess ((n, 2), OPTFLOW_USE_INITIAL_FLOW): erp_klt_track_guess, the search starts at the guesses.
+        rot (3x3 R_cur_prev): erp_klt_track_rot, the search starts where the rotation takes each point;
+        -> (next, status, err, the start positions used)."""
         prev = _u8rows(prev)
         curr = _u8rows(curr, prev.strides[0])
         H, W = prev.shape
@@ -551,7 +566,23 @@ class Context:
         st = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32)
         prm = params or default_klt_params()
-        if seam is None:
+        if guess is not None and rot is not None:
+            raise VioError("klt_track: guess and rot exclude each other")
+        if guess is not None:
+            g = np.ascontiguousarray(guess, np.float32).reshape(-1, 2)
+            if len(g) != n:
+                raise VioError("klt_track: one guess per point")
+            self.check(lib().erp_klt_track_guess(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), _p(g), n,
+                                                 _p(nxt), _p(st), _p(err), C.byref(prm),
+                                                 VIO_SEAM_CUT if seam is None else int(seam)), "erp_klt_track_guess")
+        elif rot is not None:
+            R = np.ascontiguousarray(rot, np.float32).reshape(9)
+            used = np.zeros((n, 2), np.float32)
+            self.check(lib().erp_klt_track_rot(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), n, _p(R),
+                                               _p(nxt), _p(st), _p(err), _p(used), C.byref(prm),
+                                               VIO_SEAM_CUT if seam is None else int(seam)), "erp_klt_track_rot")
+            return nxt, st, err, used
+        elif seam is None:
             self.check(lib().erp_klt_track(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts), n, _p(nxt),
                                            _p(st), _p(err), C.byref(prm)), "erp_klt_track")
         else:
@@ -959,6 +990,18 @@ class Warp:
             pass
 
 
+def predict_from_preint(preint, T_BC):
+    """erp_predict_from_preint (host only): R_cur_prev = R_BC^T delta_R^T R_BC, (3, 3) float32, from the
+    preintegration between two frames (a VioPreint, or its 3x3 delta_R) and the camera-to-body T_BC (4x4)."""
+    pre = preint if isinstance(preint, abi.VioPreint) else abi.preint_from_delta_R(preint)
+    T = np.ascontiguousarray(T_BC, np.float32).reshape(16)
+    R = np.zeros(9, np.float32)
+    rc = lib().erp_predict_from_preint(C.byref(pre), _p(T), _p(R))
+    if rc != 0:
+        raise VioError(f"erp_predict_from_preint failed ({rc}): delta_R or T_BC's rotation block is not a rotation")
+    return R.reshape(3, 3)
+
+
 class Tracker:
     """Device-resident frame pipeline (erp_tracker_*): pyramids + LK + RANSAC + GFTT re-detection."""
 
@@ -1032,6 +1075,22 @@ class Tracker:
         self.n = len(pts)
         self._pts = pts
         self.ctx.check(lib().erp_tracker_set_points(self.h, _p(pts), self.n), "erp_tracker_set_points")
+
+    def set_guess(self, guess):
+        """erp_tracker_set_guess: the next run's LK starts at guess[i] (one per set_points point); that run only."""
+        g = np.ascontiguousarray(guess, np.float32).reshape(-1, 2)
+        self.ctx.check(lib().erp_tracker_set_guess(self.h, _p(g), len(g)), "erp_tracker_set_guess")
+
+    def set_rotation(self, R_cur_prev):
+        """erp_tracker_set_rotation: the next run's LK starts where R_cur_prev (3x3) takes each point; that run only."""
+        R = np.ascontiguousarray(R_cur_prev, np.float32).reshape(9)
+        self.ctx.check(lib().erp_tracker_set_rotation(self.h, _p(R)), "erp_tracker_set_rotation")
+
+    def download_guess(self):
+        """erp_tracker_download_guess: the start positions the last (guided) run used, (n, 2) float32."""
+        g = np.zeros((max(self.n, 1), 2), np.float32)
+        self.ctx.check(lib().erp_tracker_download_guess(self.h, _p(g)), "erp_tracker_download_guess")
+        return g[:self.n]
 
     def run(self, params=None, klt=None):
         prm = params or default_tracker_params()
@@ -1113,6 +1172,12 @@ class Frontend:
         """erp_frontend_set_seam: VIO_SEAM_CUT (default) or VIO_SEAM_WRAP (features are tracked and detected across
         the ERP seam), from the next frame on."""
         self.ctx.check(lib().erp_frontend_set_seam(self.h, int(seam)), "erp_frontend_set_seam")
+
+    def predict_rotation(self, R_cur_prev):
+        """erp_frontend_predict_rotation: the next track* call's LK starts where R_cur_prev (3x3, e.g. from
+        predict_from_preint) takes each feature; that call only."""
+        R = np.ascontiguousarray(R_cur_prev, np.float32).reshape(9)
+        self.ctx.check(lib().erp_frontend_predict_rotation(self.h, _p(R)), "erp_frontend_predict_rotation")
 
     def track(self, img):
         img = _u8img(img)

@@ -161,6 +161,13 @@ def preints_to_c(preints):
     return arr, valid
 
 
+def preint_from_delta_R(delta_R):
+    """a VioPreint that carries only delta_R (3x3), all erp_predict_from_preint reads"""
+    e = VioPreint()
+    e.delta_R[:] = np.asarray(delta_R, np.float32).reshape(9).tolist()
+    return e
+
+
 IMU_FACTOR_ARRAYS = (("gravity", 3), ("delta_i", 6), ("v_i", 3), ("bg", 3), ("ba", 3), ("delta_j", 6), ("v_j", 3))
 
 

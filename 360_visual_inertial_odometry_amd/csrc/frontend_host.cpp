@@ -94,6 +94,8 @@ struct erp_frontend {
     std::vector<FeatureRec> feats;
     erp_equalize_params eq{};  // erp_frontend_set_equalize; mode VIO_EQ_NONE: off
     int seam = VIO_SEAM_CUT;   // erp_frontend_set_seam (the tracker's mode follows it)
+    bool has_pred = false;     // erp_frontend_predict_rotation: R_cur_prev of the next track call only
+    float pred_rot[9] = {};
 };
 
 namespace {
@@ -140,6 +142,8 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
     hipStream_t st = ctx->stream;
     int rc;
     const erp_frontend_params& P = f->p;
+    const bool predicted = f->has_pred;  // this call's prediction, consumed whatever the call does
+    f->has_pred = false;
     if (f->eq.mode != VIO_EQ_NONE && (rc = erp_tracker_equalize(t, 1, &f->eq))) return rc;
     if (f->frame == 0 || f->feats.empty()) {
         // first frame (or nothing to track): detect only (:68-97)
@@ -159,6 +163,7 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
         for (int i = 0; i < n; ++i) { prev[2 * i] = f->feats[i].x; prev[2 * i + 1] = f->feats[i].y; }
         if ((rc = erp_tracker_set_points(t, prev.data(), n))) return rc;
         erp_klt_params kp{21, 3, 30, 0.01f, 0.01f, 0};  // FeatureTracker.cpp:33-35, 240
+        if (predicted && (rc = tracker_set_rotation(t, f->pred_rot, "erp_frontend_predict_rotation"))) return rc;
         if ((rc = enqueue_lk(t, &kp, n))) return rc;
         VIO_HIP(ctx, hipMemcpyAsync(next.data(), t->d_next, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
         VIO_HIP(ctx, hipMemcpyAsync(status.data(), t->d_status, n, hipMemcpyDeviceToHost, st));
@@ -297,6 +302,18 @@ int erp_frontend_set_seam(erp_frontend* f, int seam) {
     if (rc) return rc;
     if ((rc = erp_tracker_set_seam(f->t, seam))) return rc;
     f->seam = seam;
+    return VIO_OK;
+}
+
+int erp_frontend_predict_rotation(erp_frontend* f, const float R_cur_prev[9]) {
+    if (!f) return VIO_EINVAL;
+    if (!R_cur_prev || !is_rotation(R_cur_prev)) {
+        set_error(f->t->ctx, R_cur_prev ? "erp_frontend_predict_rotation: R_cur_prev is not a rotation"
+                                        : "erp_frontend_predict_rotation: null R_cur_prev");
+        return VIO_EINVAL;
+    }
+    std::copy(R_cur_prev, R_cur_prev + 9, f->pred_rot);
+    f->has_pred = true;
     return VIO_OK;
 }
 

@@ -301,10 +301,51 @@ __device__ void lk_aux(const LkAux& X, int b) {
     }
 }
 
+// Guided search: the start position (gx, gy) of point pt at the top level, in level-0 pixels; on entry the point's
+// previous position (px, py), which stays when the point has no usable guess.  Workgroup-uniform.
+//   LK_GUESS_PTS  A.guess[pt]
+//   LK_GUESS_ROT  Camera::BearingToPixel(R * PixelToBearing(prev)) (Camera.cpp:22-67) in f32, operations in this
+//                 order: r_i = ((R_i0 b0 + R_i1 b1) + R_i2 b2), theta = atan2f(r0, r2), phi = -asinf(r1 / |r|),
+//                 u = W (0.5 + theta / 2pi), v = H (0.5 - phi / pi)
+// A guess that is not finite or lies outside [-W, 2W) x [-H, 2H) counts as absent (OpenCV would index with it).
+// WRAP: x folded into [0, W) by one f32 +-W, as the final fold of the tracked column.
+template <bool WRAP>
+__device__ __forceinline__ void lk_guess(const LkArgs& A, int pt, float px, float py, float& gx, float& gy) {
+    const int W = A.lv[0].w, H = A.lv[0].h;
+    const float Wf = (float)W, Hf = (float)H;
+    float u, v;
+    if (A.guided == LK_GUESS_ROT) {
+        float b[3];
+        pixel_to_bearing(px, py, W, H, b);
+        const float r0 = (A.rot[0] * b[0] + A.rot[1] * b[1]) + A.rot[2] * b[2];
+        const float r1 = (A.rot[3] * b[0] + A.rot[4] * b[1]) + A.rot[5] * b[2];
+        const float r2 = (A.rot[6] * b[0] + A.rot[7] * b[1]) + A.rot[8] * b[2];
+        const float nr = sqrtf((r0 * r0 + r1 * r1) + r2 * r2);
+        const float theta = atan2f(r0, r2);
+        const float phi = -asinf(fminf(fmaxf(r1 / nr, -1.f), 1.f));
+        u = Wf * (0.5f + theta / 6.2831855f);
+        v = Hf * (0.5f - phi / 3.1415927f);
+    } else {
+        u = A.guess[2 * pt];
+        v = A.guess[2 * pt + 1];
+    }
+    if (!(u >= -Wf && u < 2.f * Wf && v >= -Hf && v < 2.f * Hf)) return;  // (a NaN fails every comparison)
+    if (WRAP) {
+        if (u < 0.f) u += Wf;
+        else if (u >= Wf) u -= Wf;
+        if (u == Wf) u = 0.f;  // (a tiny negative column rounds up to W)
+    }
+    gx = u;
+    gy = v;
+}
+
 // WRAP (seam wrap mode, A.x_wrap): every level is the periodic continuation of the frame in x -- tile columns
 // modulo the level width, no "left the frame" test in x, the iteration in unwrapped coordinates; only the final
 // next.x is folded into [0, W) by one f32 +-W.  The default instance is the code it was before the mode existed.
-template <bool WRAP>
+// GUIDED (OPTFLOW_USE_INITIAL_FLOW, A.guided): the top level starts at the point's guess (lk_guess) instead of its
+// previous position; nothing else differs, and a guess equal to the previous position gives the unguided bits.  The
+// two unguided instances are the code they were before the guided ones existed.
+template <bool WRAP, bool GUIDED = false>
 __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
     __shared__ LkShared S;
     __shared__ double red[LK_WAVES];
@@ -322,6 +363,14 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
     float nxt_x = 0.f, nxt_y = 0.f;
     int status = 1;
     float err = 0.f;
+    float gs_x = prev_x, gs_y = prev_y;  // GUIDED: the top level's start position in level-0 pixels
+    if constexpr (GUIDED) {
+        lk_guess<WRAP>(A, pt, prev_x, prev_y, gs_x, gs_y);
+        if (A.guess_out && tid == 128) {
+            A.guess_out[2 * pt] = gs_x;
+            A.guess_out[2 * pt + 1] = gs_y;
+        }
+    }
     for (int level = A.levels; level >= 0; --level) {
         const LkLevel& Lv = A.lv[level];
         const int w = Lv.w, h = Lv.h;
@@ -330,8 +379,10 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
         const float sc = (float)(1. / (1 << level));
         float px = prev_x * sc, py = prev_y * sc;
         float nx, ny;
-        if (level == A.levels) { nx = px; ny = py; }
-        else { nx = nxt_x * 2.f; ny = nxt_y * 2.f; }
+        if (level == A.levels) {
+            if constexpr (GUIDED) { nx = gs_x * sc; ny = gs_y * sc; }
+            else { nx = px; ny = py; }
+        } else { nx = nxt_x * 2.f; ny = nxt_y * 2.f; }
         nxt_x = nx; nxt_y = ny;
         px -= hw; py -= hw;
         const int ipx = (int)floorf(px), ipy = (int)floorf(py);
@@ -2343,7 +2394,10 @@ hipError_t launch_lk(const LkArgs& a, hipStream_t st, const LkAux* aux) {
     if (aux) x = *aux;
     const int n = a.n > 0 ? a.n : 0, blocks = n + (aux ? LK_AUX_BLOCKS : 0);
     if (blocks == 0) return hipSuccess;
-    if (a.x_wrap) hipLaunchKernelGGL(lk_kernel<true>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
+    if (a.guided != LK_GUESS_NONE) {
+        if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, true>), dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
+        else hipLaunchKernelGGL((lk_kernel<false, true>), dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
+    } else if (a.x_wrap) hipLaunchKernelGGL(lk_kernel<true>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
     else hipLaunchKernelGGL(lk_kernel<false>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
     return hipGetLastError();
 }

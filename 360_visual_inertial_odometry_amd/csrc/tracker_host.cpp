@@ -164,6 +164,8 @@ static int tracker_alloc(erp_tracker* t) {
     if ((rc = dalloc(t, &t->d_pts, sizeof(float) * 2 * P))) return rc;
     if ((rc = dalloc(t, &t->d_next, sizeof(float) * 2 * P))) return rc;
     if ((rc = dalloc(t, &t->d_err, sizeof(float) * P))) return rc;
+    if ((rc = dalloc(t, &t->d_guess, sizeof(float) * 2 * P))) return rc;
+    if ((rc = dalloc(t, &t->d_guess_out, sizeof(float) * 2 * P))) return rc;
     if ((rc = dalloc(t, &t->d_status, P))) return rc;
     if ((rc = dalloc(t, &t->d_kept, P))) return rc;
     if ((rc = dalloc(t, &t->d_gidx, sizeof(int) * P))) return rc;
@@ -256,6 +258,15 @@ int enqueue_lk(erp_tracker* t, const erp_klt_params* p, int n, bool pyr_built, c
     a.min_eig = p->min_eig_threshold;
     a.x_wrap = t->seam;
     if (aux) a.bear1 = t->d_bear1;  // the pipeline's RANSAC input (its previous points' bearings: aux workgroups)
+    // a prediction belongs to this launch alone
+    a.guided = t->pred;
+    if (a.guided != LK_GUESS_NONE) {
+        a.guess = t->d_guess;
+        std::memcpy(a.rot, t->pred_rot, sizeof a.rot);
+        a.guess_out = t->d_guess_out;
+    }
+    t->guess_out_valid = a.guided != LK_GUESS_NONE;
+    t->pred = LK_GUESS_NONE;
     if (t->ev[1] && (!aux || t->stage_timing)) (void)hipEventRecord(t->ev[1], t->ctx->stream);
     hipError_t e = launch_lk(a, t->ctx->stream, aux);
     if (e != hipSuccess) return hip_fail(t->ctx, e, "lk_kernel");
@@ -520,6 +531,32 @@ int read_corners(erp_tracker* t, float* out_xy, int* n_out) {
     return VIO_OK;
 }
 
+bool is_rotation(const float R[9]) {
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R[i])) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 3; ++k) s += (double)R[3 * k + i] * (double)R[3 * k + j];
+            if (std::fabs(s - (i == j ? 1.0 : 0.0)) > 1e-3) return false;
+        }
+    const double det = (double)R[0] * ((double)R[4] * R[8] - (double)R[5] * R[7]) -
+                       (double)R[1] * ((double)R[3] * R[8] - (double)R[5] * R[6]) +
+                       (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
+    return det > 0.0;
+}
+
+int tracker_set_rotation(erp_tracker* t, const float R[9], const char* who) {
+    if (!t) return VIO_EINVAL;
+    if (!R || !is_rotation(R)) {
+        set_error(t->ctx, std::string(who) + (R ? ": R_cur_prev is not a rotation" : ": null R_cur_prev"));
+        return VIO_EINVAL;
+    }
+    std::memcpy(t->pred_rot, R, sizeof t->pred_rot);
+    t->pred = LK_GUESS_ROT;
+    return VIO_OK;
+}
+
 int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who) {
     if (seam != VIO_SEAM_CUT && seam != VIO_SEAM_WRAP) {
         set_error(ctx, std::string(who) + ": unknown seam mode");
@@ -637,6 +674,38 @@ int erp_tracker_set_points(erp_tracker* t, const float* pts, int n) {
     return VIO_OK;
 }
 
+int erp_tracker_set_guess(erp_tracker* t, const float* guess, int n) {
+    if (!t) return VIO_EINVAL;
+    if (!guess || n != t->n_pts) {
+        set_error(t->ctx, guess ? "erp_tracker_set_guess: n is not the erp_tracker_set_points count"
+                                : "erp_tracker_set_guess: null guess");
+        return VIO_EINVAL;
+    }
+    VIO_DEVICE(t->ctx);
+    if (n)
+        VIO_HIP(t->ctx, hipMemcpyAsync(t->d_guess, guess, sizeof(float) * 2 * n, hipMemcpyHostToDevice, t->ctx->stream));
+    t->pred = LK_GUESS_PTS;
+    return VIO_OK;
+}
+
+int erp_tracker_set_rotation(erp_tracker* t, const float R_cur_prev[9]) {
+    return tracker_set_rotation(t, R_cur_prev, "erp_tracker_set_rotation");
+}
+
+int erp_tracker_download_guess(erp_tracker* t, float* guess) {
+    if (!t) return VIO_EINVAL;
+    if (!guess || !t->guess_out_valid) {
+        set_error(t->ctx, guess ? "erp_tracker_download_guess: the last run had no prediction"
+                                : "erp_tracker_download_guess: null guess");
+        return VIO_EINVAL;
+    }
+    VIO_DEVICE(t->ctx);
+    VIO_HIP(t->ctx, hipStreamSynchronize(t->ctx->stream));
+    if (t->n_pts)
+        VIO_HIP(t->ctx, hipMemcpy(guess, t->d_guess_out, sizeof(float) * 2 * t->n_pts, hipMemcpyDeviceToHost));
+    return VIO_OK;
+}
+
 // the enqueue sequence of one pipeline run
 static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_tracker_params* p, int n, int radius,
                        const GfttPlan& pl) {
@@ -716,8 +785,16 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
     return enqueue_gftt(t, pl);
 }
 
+static int tracker_run(erp_tracker* t, const erp_klt_params* klt, const erp_tracker_params* p);
+
 int erp_tracker_run(erp_tracker* t, const erp_klt_params* klt, const erp_tracker_params* p) {
     if (!t || !p) return VIO_EINVAL;
+    const int rc = tracker_run(t, klt, p);
+    t->pred = LK_GUESS_NONE;  // a prediction belongs to this run, also when the run is refused
+    return rc;
+}
+
+static int tracker_run(erp_tracker* t, const erp_klt_params* klt, const erp_tracker_params* p) {
     int rc = check_klt(t->ctx, klt);
     if (rc) return rc;
     if (p->ransac_iters < 0 || p->max_corners < 0 || p->max_corners > t->max_corners || p->quality <= 0 ||
@@ -816,30 +893,94 @@ int erp_klt_track(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W,
     return erp_klt_track_seam(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, VIO_SEAM_CUT);
 }
 
-int erp_klt_track_seam(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
-                       const float* pts, int n, float* next, uint8_t* status, float* err, const erp_klt_params* params,
-                       int seam) {
-    if (!ctx || !prev || !curr || n < 0 || (n > 0 && (!pts || !next || !status))) return VIO_EINVAL;
+// the one-shot LK calls: a tracker for the call, the two frames, the points, one LK launch.  guess / R: the guided
+// forms (at most one of them); guess_out: the start positions used (guided only, may be null)
+static int klt_track_once(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                          const float* pts, int n, float* next, uint8_t* status, float* err,
+                          const erp_klt_params* params, int seam, const float* guess, const float* R,
+                          float* guess_out, const char* who) {
     int rc = check_klt(ctx, params);
     if (rc) return rc;
-    if ((rc = seam_mode_ok(ctx, seam, W, H, params->win, params->max_level, 0.0, "erp_klt_track_seam"))) return rc;
+    if ((rc = seam_mode_ok(ctx, seam, W, H, params->win, params->max_level, 0.0, who))) return rc;
+    if (R && !is_rotation(R)) {
+        set_error(ctx, std::string(who) + ": R_cur_prev is not a rotation");
+        return VIO_EINVAL;
+    }
     VIO_DEVICE(ctx);
     erp_tracker* t = nullptr;
     if ((rc = erp_tracker_create(ctx, W, H, std::max(n, 1), 0, &t))) return rc;
     t->seam = seam;
     if (!(rc = upload_frame(t, 0, prev, stride)) && !(rc = upload_frame(t, 1, curr, stride)) &&
-        !(rc = erp_tracker_set_points(t, pts, n)) && !(rc = enqueue_lk(t, params, n))) {
+        !(rc = erp_tracker_set_points(t, pts, n)) && !(rc = guess ? erp_tracker_set_guess(t, guess, n) : VIO_OK) &&
+        !(rc = R ? tracker_set_rotation(t, R, who) : VIO_OK) && !(rc = enqueue_lk(t, params, n))) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = hip_fail(ctx, e, "erp_klt_track");
         else if (n) {
             if (hipMemcpy(next, t->d_next, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess ||
                 hipMemcpy(status, t->d_status, n, hipMemcpyDeviceToHost) != hipSuccess ||
-                (err && hipMemcpy(err, t->d_err, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess))
+                (err && hipMemcpy(err, t->d_err, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (guess_out &&
+                 hipMemcpy(guess_out, t->d_guess_out, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess))
                 rc = hip_fail(ctx, hipErrorUnknown, "erp_klt_track download");
         }
     }
     erp_tracker_destroy(t);
     return rc;
+}
+
+int erp_klt_track_seam(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                       const float* pts, int n, float* next, uint8_t* status, float* err, const erp_klt_params* params,
+                       int seam) {
+    if (!ctx || !prev || !curr || n < 0 || (n > 0 && (!pts || !next || !status))) return VIO_EINVAL;
+    return klt_track_once(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, seam, nullptr, nullptr,
+                          nullptr, "erp_klt_track_seam");
+}
+
+int erp_klt_track_guess(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                        const float* pts, const float* guess, int n, float* next, uint8_t* status, float* err,
+                        const erp_klt_params* params, int seam) {
+    if (!ctx) return VIO_EINVAL;
+    if (!prev || !curr || n < 0 || !guess || (n > 0 && (!pts || !next || !status))) {
+        set_error(ctx, "erp_klt_track_guess: null frame, points, guess or output, or n < 0");
+        return VIO_EINVAL;
+    }
+    return klt_track_once(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, seam, guess, nullptr,
+                          nullptr, "erp_klt_track_guess");
+}
+
+int erp_klt_track_rot(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                      const float* pts, int n, const float R_cur_prev[9], float* next, uint8_t* status, float* err,
+                      float* guess_out, const erp_klt_params* params, int seam) {
+    if (!ctx) return VIO_EINVAL;
+    if (!prev || !curr || n < 0 || !R_cur_prev || (n > 0 && (!pts || !next || !status))) {
+        set_error(ctx, "erp_klt_track_rot: null frame, points, rotation or output, or n < 0");
+        return VIO_EINVAL;
+    }
+    return klt_track_once(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, seam, nullptr, R_cur_prev,
+                          guess_out, "erp_klt_track_rot");
+}
+
+int erp_predict_from_preint(const vio_preint* pre, const float* T_BC, float R_cur_prev[9]) {
+    if (!pre || !T_BC || !R_cur_prev) return VIO_EINVAL;
+    float Rbc[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rbc[3 * i + j] = T_BC[4 * i + j];
+    if (!is_rotation(pre->delta_R) || !is_rotation(Rbc)) return VIO_EINVAL;
+    // R_cur_prev = R_BC^T delta_R^T R_BC in f64, rounded once
+    double M[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 3; ++k) s += (double)pre->delta_R[3 * k + i] * (double)Rbc[3 * k + j];
+            M[3 * i + j] = s;  // delta_R^T R_BC
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < 3; ++k) s += (double)Rbc[3 * k + i] * M[3 * k + j];
+            R_cur_prev[3 * i + j] = (float)s;
+        }
+    return VIO_OK;
 }
 
 int erp_gftt(vio_ctx* ctx, const uint8_t* img, const uint8_t* mask, int W, int H, int stride, int max_corners,

@@ -76,6 +76,12 @@ struct erp_tracker {
     bool has_mask = false;
     uint8_t* d_usable = nullptr;
     int seam = VIO_SEAM_CUT;  // erp_tracker_set_seam: VIO_SEAM_WRAP runs every stage on the periodic continuation
+    // the prediction of the next LK launch (erp_tracker_set_guess / erp_tracker_set_rotation): enqueue_lk takes
+    // the guided instance when one is held and clears it once the launch is enqueued
+    int pred = vio360::LK_GUESS_NONE;
+    float pred_rot[9] = {};
+    float *d_guess = nullptr, *d_guess_out = nullptr;  // [max_points][2]: explicit guesses / start positions used
+    bool guess_out_valid = false;                      // the last LK launch was guided and wrote d_guess_out
     // GFTT top-K fast path
     unsigned int* d_hist = nullptr;
     unsigned long long *d_topk = nullptr, *d_topk_sorted = nullptr;
@@ -109,6 +115,10 @@ namespace vio360 {
 int ensure_iters(erp_tracker* t, int iters);
 // CreateFeatureMask's disc half-widths for `radius` in d_halfw (a blocking upload when the radius changes)
 int ensure_halfw(erp_tracker* t, int radius);
+// R is a rotation: |R^T R - I| <= 1e-3 in every entry and det R > 0 (f64 on the f32 entries)
+bool is_rotation(const float R[9]);
+// the tracker's next LK launch starts every point at BearingToPixel(R_cur_prev * PixelToBearing(prev))
+int tracker_set_rotation(erp_tracker* t, const float R_cur_prev[9], const char* who);
 int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who);
 // Brings the frame into slot `slot` as the tracker's W x H grey image, all on the context stream.
 int tracker_ingest(erp_tracker* t, int slot, const FrameSrc& f, const char* who);

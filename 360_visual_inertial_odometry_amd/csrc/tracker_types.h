@@ -41,7 +41,16 @@ struct LkArgs {
     double eps2;
     float* bear1;  // [n][3] or null: the bearing of each tracked point (tracker pipeline: RANSAC's input)
     int x_wrap;    // seam wrap mode: columns modulo the level width, no sideways exit, next.x folded into [0, W)
+    // guided search (OPTFLOW_USE_INITIAL_FLOW; the GUIDED instances of lk_kernel, launched when guided != 0): the
+    // top level starts at the point's guess instead of its previous position.  The guess is guess[pt] (LK_GUESS_PTS)
+    // or BearingToPixel(rot * PixelToBearing(prev)) formed by the point's own workgroup (LK_GUESS_ROT).  A guess that
+    // is not finite or lies outside [-W, 2W) x [-H, 2H) counts as absent; in seam wrap mode x is folded into [0, W).
+    int guided;          // LK_GUESS_NONE / LK_GUESS_PTS / LK_GUESS_ROT
+    const float* guess;  // [n][2] (LK_GUESS_PTS)
+    float rot[9];        // R_cur_prev, row-major (LK_GUESS_ROT)
+    float* guess_out;    // [n][2] or null: the start position each point actually used
 };
+constexpr int LK_GUESS_NONE = 0, LK_GUESS_PTS = 1, LK_GUESS_ROT = 2;
 
 struct RansacArgs {
     const float* p0;       // [n][2] previous points

@@ -979,6 +979,51 @@ int erp_tracker_set_seam(erp_tracker* t, int seam);
    check is made here, with the front end's LK parameters (21 / 3) and min_distance. */
 int erp_frontend_set_seam(erp_frontend* f, int seam);
 
+/* Guided LK: the search of a point starts at a predicted position instead of its previous one, so the
+   tracker survives an inter-frame rotation beyond the pyramid's reach (about 40 px per frame at win 21, 3 levels).
+     explicit guesses  cv::calcOpticalFlowPyrLK(..., OPTFLOW_USE_INITIAL_FLOW): at the top pyramid level the search
+                       starts at guess * (float)(1. / (1 << level)) instead of prev * that; window sums, iteration,
+                       status and err rules and the level hand-down next * 2 are unchanged.  guess == pts gives the
+                       unguided result bit for bit (in VIO_SEAM_WRAP: for points inside [0, W), see the fold below).
+     rotation          R_cur_prev (3x3 f32, row-major) takes a bearing of the previous camera frame into the current
+                       one; the guess of a point is BearingToPixel(R_cur_prev * PixelToBearing(prev)) with
+                       Camera.cpp:22-67's conventions (theta = atan2(x, z), phi = -asin(y / |b|),
+                       u = W (0.5 + theta / 2pi), v = H (0.5 - phi / pi)), formed in f32 on the device by the
+                       point's own LK workgroup.  VIO_EINVAL unless R_cur_prev is a rotation: every entry of
+                       R^T R - I within 1e-3 and det R > 0.
+     seam modes        VIO_SEAM_WRAP folds a guess's x into [0, W) by one f32 +-W (a fold that rounds to W gives 0);
+                       VIO_SEAM_CUT takes it as it is, and a guess outside the frame ends the level as the
+                       "left the frame" tests end it.
+     bad guesses       a guess that is not finite, or lies outside [-W, 2W) x [-H, 2H), counts as absent: that point
+                       starts at its previous position.  A DEVIATION from OpenCV, which would index with it; it
+                       keeps every tile origin within the ranges the index arithmetic was written for.
+     lifetime          on a tracker or a front end a prediction belongs to one frame pair: the next run / track call
+                       consumes it and clears it.  Without one every entry point behaves as it always did.
+   Argument errors (a null pointer, a wrong n, a non-rotation, an unknown seam mode, a size the seam mode does not
+   admit) return VIO_EINVAL before anything is launched. */
+/* one-shot, like erp_klt_track_seam; guess[n][2] */
+int erp_klt_track_guess(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                        const float* pts, const float* guess, int n, float* next, uint8_t* status, float* err,
+                        const erp_klt_params* params, int seam);
+/* the same, seeded by a rotation; guess_out[n][2] (may be NULL): the start position each point used, after the fold
+   and the bad-guess rule */
+int erp_klt_track_rot(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                      const float* pts, int n, const float R_cur_prev[9], float* next, uint8_t* status, float* err,
+                      float* guess_out, const erp_klt_params* params, int seam);
+/* device pipeline: for the next erp_tracker_run only.  n must be the erp_tracker_set_points count; the later of
+   set_guess / set_rotation wins. */
+int erp_tracker_set_guess(erp_tracker* t, const float* guess, int n);
+int erp_tracker_set_rotation(erp_tracker* t, const float R_cur_prev[9]);
+/* the start positions of the last run [n][2]; VIO_EINVAL when that run had no prediction */
+int erp_tracker_download_guess(erp_tracker* t, float* guess);
+/* front end: for the next erp_frontend_track* call only (a call that only detects consumes it too) */
+int erp_frontend_predict_rotation(erp_frontend* f, const float R_cur_prev[9]);
+/* host only: R_cur_prev = R_BC^T * delta_R^T * R_BC from the preintegration between the two frames
+   (delta_R = R_b(prev)^T R_b(cur), IMUPreintegrator.cpp:227; T_BC camera-to-body 4x4 row-major,
+   T_wc = T_wb * T_BC, Frame.cpp:87), formed in f64 and rounded once.  VIO_EINVAL when delta_R or T_BC's rotation
+   block is not a rotation (the test above). */
+int erp_predict_from_preint(const vio_preint* between_frames, const float* T_BC, float R_cur_prev[9]);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

@@ -14,7 +14,9 @@ from . import abi
 from .abi import (VIO_BA_FULL, VIO_BA_LOCAL, VIO_BA_VI, VIO_PNP, VIO_SEAM_CUT, VIO_SEAM_WRAP, BaOutput,  # noqa: F401
                   BaProblem,
                   ErpFrontendParams, ErpKltParams, ErpTrackerParams, default_frontend_params,
-                  default_klt_params, default_tracker_params)
+                  default_klt_params, default_tracker_params,
+                  VIO_FB_OFF, VIO_FB_ON, VIO_FB_NOT_RUN, VIO_FB_PASS, VIO_FB_BACK_LOST, VIO_FB_TOO_FAR,
+                  ErpFbParams, default_fb_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIO360_LIB") or os.path.join(_HERE, "libvio360.so")
@@ -65,6 +67,8 @@ EXPORTS = [
     "erp_seam_check", "erp_klt_track_seam", "erp_gftt_seam", "erp_tracker_set_seam", "erp_frontend_set_seam",
     "erp_klt_track_guess", "erp_klt_track_rot", "erp_tracker_set_guess", "erp_tracker_set_rotation",
     "erp_tracker_download_guess", "erp_frontend_predict_rotation", "erp_predict_from_preint",
+    "erp_fb_check", "erp_klt_track_fb", "erp_tracker_set_fb", "erp_tracker_download_fb", "erp_frontend_set_fb",
+    "erp_frontend_fb_stats",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -216,6 +220,15 @@ def lib():
         L.erp_tracker_download_guess.argtypes = [vp, vp]
         L.erp_frontend_predict_rotation.argtypes = [vp, vp]
         L.erp_predict_from_preint.argtypes = [C.POINTER(abi.VioPreint), vp, vp]
+    if hasattr(L, "erp_fb_check") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        fbp = C.POINTER(abi.ErpFbParams)
+        L.erp_fb_check.argtypes = [fbp]
+        L.erp_klt_track_fb.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp,
+                                       C.POINTER(abi.ErpKltParams), C.c_int, fbp]
+        L.erp_tracker_set_fb.argtypes = [vp, fbp]
+        L.erp_tracker_download_fb.argtypes = [vp, vp, vp, vp]
+        L.erp_frontend_set_fb.argtypes = [vp, fbp]
+        L.erp_frontend_fb_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -551,12 +564,14 @@ class Context:
         return _kernel_ms(self, self.h, "erp_resize_area_kernel_ms")
 
     # ---- ERP feature tracking ----
-    def klt_track(self, prev, curr, pts, params=None, seam=None, guess=None, rot=None):
+    def klt_track(self, prev, curr, pts, params=None, seam=None, guess=None, rot=None, fb=None):
         """cv::calcOpticalFlowPyrLK as FeatureTracker::TrackOpticalFlow calls it -> (next, status, err).
         seam (VIO_SEAM_*): erp_klt_track_seam; VIO_SEAM_WRAP tracks across the ERP seam, next.x in [0, W).
         guess ((n, 2), OPTFLOW_USE_INITIAL_FLOW): erp_klt_track_guess, the search starts at the guesses.
         rot (3x3 R_cur_prev): erp_klt_track_rot, the search starts where the rotation takes each point;
-        -> (next, status, err, the start positions used)."""
+        -> (next, status, err, the start positions used).
+        fb (ErpFbParams, default_fb_params()): erp_klt_track_fb, the round-trip check (with guess or without; not with
+        rot) -> (next, status, err, back, fb_state, fb_d2), status = forward AND pass."""
         prev = _u8rows(prev)
         curr = _u8rows(curr, prev.strides[0])
         H, W = prev.shape
@@ -568,6 +583,23 @@ class Context:
         prm = params or default_klt_params()
         if guess is not None and rot is not None:
             raise VioError("klt_track: guess and rot exclude each other")
+        if fb is not None:
+            if rot is not None:
+                raise VioError("klt_track: fb takes guesses, not rot (feed erp_klt_track_rot's start positions back)")
+            g = None
+            if guess is not None:
+                g = np.ascontiguousarray(guess, np.float32).reshape(-1, 2)
+                if len(g) != n:
+                    raise VioError("klt_track: one guess per point")
+            back = np.zeros((n, 2), np.float32)
+            state = np.zeros(n, np.uint8)
+            d2 = np.zeros(n, np.float32)
+            self.check(lib().erp_klt_track_fb(self.h, _p(prev), _p(curr), W, H, prev.strides[0], _p(pts),
+                                              _p(g) if g is not None else None, n, _p(nxt), _p(st), _p(err), _p(back),
+                                              _p(state), _p(d2), C.byref(prm),
+                                              VIO_SEAM_CUT if seam is None else int(seam), C.byref(fb)),
+                       "erp_klt_track_fb")
+            return nxt, st, err, back, state, d2
         if guess is not None:
             g = np.ascontiguousarray(guess, np.float32).reshape(-1, 2)
             if len(g) != n:
@@ -1086,6 +1118,18 @@ class Tracker:
         R = np.ascontiguousarray(R_cur_prev, np.float32).reshape(9)
         self.ctx.check(lib().erp_tracker_set_rotation(self.h, _p(R)), "erp_tracker_set_rotation")
 
+    def set_fb(self, fb):
+        """erp_tracker_set_fb: the round-trip check (ErpFbParams) of every later run, until set again."""
+        self.ctx.check(lib().erp_tracker_set_fb(self.h, C.byref(fb)), "erp_tracker_set_fb")
+
+    def download_fb(self):
+        """erp_tracker_download_fb: (back (n, 2), fb_state (n,), fb_d2 (n,)) of the last run; raises when that run
+        had the check off."""
+        m = max(self.n, 1)
+        back, state, d2 = np.zeros((m, 2), np.float32), np.zeros(m, np.uint8), np.zeros(m, np.float32)
+        self.ctx.check(lib().erp_tracker_download_fb(self.h, _p(back), _p(state), _p(d2)), "erp_tracker_download_fb")
+        return back[:self.n], state[:self.n], d2[:self.n]
+
     def download_guess(self):
         """erp_tracker_download_guess: the start positions the last (guided) run used, (n, 2) float32."""
         g = np.zeros((max(self.n, 1), 2), np.float32)
@@ -1172,6 +1216,17 @@ class Frontend:
         """erp_frontend_set_seam: VIO_SEAM_CUT (default) or VIO_SEAM_WRAP (features are tracked and detected across
         the ERP seam), from the next frame on."""
         self.ctx.check(lib().erp_frontend_set_seam(self.h, int(seam)), "erp_frontend_set_seam")
+
+    def set_fb(self, fb):
+        """erp_frontend_set_fb: the round-trip check (ErpFbParams) of the LK step, from the next frame on."""
+        self.ctx.check(lib().erp_frontend_set_fb(self.h, C.byref(fb)), "erp_frontend_set_fb")
+
+    def fb_stats(self):
+        """erp_frontend_fb_stats: (checked, back_lost, too_far) of the last track call."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(lib().erp_frontend_fb_stats(self.h, C.byref(a), C.byref(b), C.byref(c)),
+                       "erp_frontend_fb_stats")
+        return a.value, b.value, c.value
 
     def predict_rotation(self, R_cur_prev):
         """erp_frontend_predict_rotation: the next track* call's LK starts where R_cur_prev (3x3, e.g. from

@@ -98,6 +98,19 @@ class ErpFrontendParams(C.Structure):
                 ("clustered_std_ratio", C.c_float), ("ransac_seed", C.c_uint32)]
 
 
+class ErpFbParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_dist", C.c_float)]
+
+
+VIO_FB_OFF, VIO_FB_ON = 0, 1
+VIO_FB_NOT_RUN, VIO_FB_PASS, VIO_FB_BACK_LOST, VIO_FB_TOO_FAR = range(4)
+
+
+def default_fb_params(max_dist=0.5):
+    """the round-trip check on, with VINS-Fusion's FLOW_BACK distance (pixels)"""
+    return ErpFbParams(VIO_FB_ON, max_dist)
+
+
 def default_frontend_params(seed=0):
     """config/default_config.yaml values the tracker reads (feature_detection.*, camera.boundary_margin,
     visualization.highlight_clustered_grid / clustered_std_ratio)."""

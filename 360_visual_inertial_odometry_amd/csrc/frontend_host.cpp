@@ -96,6 +96,9 @@ struct erp_frontend {
     int seam = VIO_SEAM_CUT;   // erp_frontend_set_seam (the tracker's mode follows it)
     bool has_pred = false;     // erp_frontend_predict_rotation: R_cur_prev of the next track call only
     float pred_rot[9] = {};
+    // erp_frontend_fb_stats: the round-trip check's counts in the last track call (zero when it ran no LK, or
+    // the check was off)
+    int fb_checked = 0, fb_back_lost = 0, fb_too_far = 0;
 };
 
 namespace {
@@ -144,6 +147,7 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
     const erp_frontend_params& P = f->p;
     const bool predicted = f->has_pred;  // this call's prediction, consumed whatever the call does
     f->has_pred = false;
+    f->fb_checked = f->fb_back_lost = f->fb_too_far = 0;
     if (f->eq.mode != VIO_EQ_NONE && (rc = erp_tracker_equalize(t, 1, &f->eq))) return rc;
     if (f->frame == 0 || f->feats.empty()) {
         // first frame (or nothing to track): detect only (:68-97)
@@ -159,7 +163,7 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
         const int n = (int)f->feats.size();
         if (n > t->max_points) { set_error(ctx, "too many features"); return VIO_ENOSYS; }
         std::vector<float> prev(2 * (size_t)n), next(2 * (size_t)n);
-        std::vector<uint8_t> status(n), usable;
+        std::vector<uint8_t> status(n), usable, fb_state;
         for (int i = 0; i < n; ++i) { prev[2 * i] = f->feats[i].x; prev[2 * i + 1] = f->feats[i].y; }
         if ((rc = erp_tracker_set_points(t, prev.data(), n))) return rc;
         erp_klt_params kp{21, 3, 30, 0.01f, 0.01f, 0};  // FeatureTracker.cpp:33-35, 240
@@ -167,12 +171,21 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
         if ((rc = enqueue_lk(t, &kp, n))) return rc;
         VIO_HIP(ctx, hipMemcpyAsync(next.data(), t->d_next, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, st));
         VIO_HIP(ctx, hipMemcpyAsync(status.data(), t->d_status, n, hipMemcpyDeviceToHost, st));
+        if (t->fb_valid) {  // the round-trip check ran: status already holds its verdict, the states are for the stats
+            fb_state.resize(n);
+            VIO_HIP(ctx, hipMemcpyAsync(fb_state.data(), t->d_fb_state, n, hipMemcpyDeviceToHost, st));
+        }
         if (t->has_mask) {  // the region mask's bit under every tracked point, gathered on the device
             usable.resize(n);
             VIO_HIP(ctx, launch_mask_gather(t->d_next, n, t->d_static, t->W, t->H, t->d_usable, st, f->seam));
             VIO_HIP(ctx, hipMemcpyAsync(usable.data(), t->d_usable, n, hipMemcpyDeviceToHost, st));
         }
         VIO_HIP(ctx, hipStreamSynchronize(st));
+        for (const uint8_t s : fb_state) {
+            f->fb_checked += s != VIO_FB_NOT_RUN;
+            f->fb_back_lost += s == VIO_FB_BACK_LOST;
+            f->fb_too_far += s == VIO_FB_TOO_FAR;
+        }
         // status ∧ !IsInPolarRegion ∧ !IsNearBoundary (:117-126; Camera.cpp:120-139)
         std::vector<int> good;
         const float m = (float)P.boundary_margin;
@@ -302,6 +315,20 @@ int erp_frontend_set_seam(erp_frontend* f, int seam) {
     if (rc) return rc;
     if ((rc = erp_tracker_set_seam(f->t, seam))) return rc;
     f->seam = seam;
+    return VIO_OK;
+}
+
+int erp_frontend_set_fb(erp_frontend* f, const erp_fb_params* fb) {
+    if (!f) return VIO_EINVAL;
+    const int rc = fb_params_ok(f->t->ctx, fb, "erp_frontend_set_fb");
+    return rc ? rc : erp_tracker_set_fb(f->t, fb);
+}
+
+int erp_frontend_fb_stats(erp_frontend* f, int* checked, int* back_lost, int* too_far) {
+    if (!f) return VIO_EINVAL;
+    if (checked) *checked = f->fb_checked;
+    if (back_lost) *back_lost = f->fb_back_lost;
+    if (too_far) *too_far = f->fb_too_far;
     return VIO_OK;
 }
 

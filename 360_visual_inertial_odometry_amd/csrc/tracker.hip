@@ -345,7 +345,26 @@ __device__ __forceinline__ void lk_guess(const LkArgs& A, int pt, float px, floa
 // GUIDED (OPTFLOW_USE_INITIAL_FLOW, A.guided): the top level starts at the point's guess (lk_guess) instead of its
 // previous position; nothing else differs, and a guess equal to the previous position gives the unguided bits.  The
 // two unguided instances are the code they were before the guided ones existed.
-template <bool WRAP, bool GUIDED = false>
+// FB (round-trip check, A.fb): after the forward search and its fold the workgroup of a found point runs the level
+// loop once more with the frames' roles swapped -- the point its own next, the top level started at the previous
+// position (always "guided") -- then tests where it lands against the previous position.  next, err, guess_out and
+// bear1 are the forward search's; status is stored once, as forward AND pass.  The LDS tiles and red are reused;
+// every branch on status is workgroup-uniform.  The four instances without FB are the code they were.
+// The rules a guess passes, for the backward direction of the round-trip check (lk_guess applies the same to its
+// own): (u, v) replaces (gx, gy) unless it is not finite or lies outside [-W, 2W) x [-H, 2H); WRAP folds x into [0, W).
+template <bool WRAP>
+__device__ __forceinline__ void lk_guess_at(float Wf, float Hf, float u, float v, float& gx, float& gy) {
+    if (!(u >= -Wf && u < 2.f * Wf && v >= -Hf && v < 2.f * Hf)) return;  // (a NaN fails every comparison)
+    if (WRAP) {
+        if (u < 0.f) u += Wf;
+        else if (u >= Wf) u -= Wf;
+        if (u == Wf) u = 0.f;  // (a tiny negative column rounds up to W)
+    }
+    gx = u;
+    gy = v;
+}
+
+template <bool WRAP, bool GUIDED = false, bool FB = false>
 __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
     __shared__ LkShared S;
     __shared__ double red[LK_WAVES];
@@ -371,16 +390,22 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
             A.guess_out[2 * pt + 1] = gs_y;
         }
     }
+    // FB: the forward result while the backward direction runs, and the check's outputs.  The second direction is
+    // a jump back to `direction`, not a loop around the level loop: without FB the label is no branch target, and
+    // the compiler emits the instructions it emitted before the check existed.
+    float fw_x = 0.f, fw_y = 0.f, fw_err = 0.f, bk_x = 0.f, bk_y = 0.f, fb_d2 = 0.f;
+    int fb_state = LK_FB_NOT_RUN, dir = 0;
+direction:
     for (int level = A.levels; level >= 0; --level) {
         const LkLevel& Lv = A.lv[level];
         const int w = Lv.w, h = Lv.h;
-        const uint8_t* I = Lv.prev;
-        const uint8_t* J = Lv.curr;
+        const uint8_t* I = FB && dir ? Lv.curr : Lv.prev;  // (the backward direction: the frames swap roles)
+        const uint8_t* J = FB && dir ? Lv.prev : Lv.curr;
         const float sc = (float)(1. / (1 << level));
         float px = prev_x * sc, py = prev_y * sc;
         float nx, ny;
         if (level == A.levels) {
-            if constexpr (GUIDED) { nx = gs_x * sc; ny = gs_y * sc; }
+            if constexpr (GUIDED || FB) { nx = gs_x * sc; ny = gs_y * sc; }
             else { nx = px; ny = py; }
         } else { nx = nxt_x * 2.f; ny = nxt_y * 2.f; }
         nxt_x = nx; nxt_y = ny;
@@ -540,6 +565,37 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
             err = 0.f;
         }
     }
+    if constexpr (FB) {
+        const float Wf = (float)A.lv[0].w, Hf = (float)A.lv[0].h;
+        if (dir == 0) {
+            fw_x = nxt_x; fw_y = nxt_y; fw_err = err;
+            if (status) {  // found (workgroup-uniform): track it back
+                // the point is its own next, the guess its previous position under lk_guess's rules.  The level
+                // loop's first LDS access follows a barrier, so the tiles and red are free as at a level change.
+                prev_x = gs_x = nxt_x;
+                prev_y = gs_y = nxt_y;
+                lk_guess_at<WRAP>(Wf, Hf, A.pts[2 * pt], A.pts[2 * pt + 1], gs_x, gs_y);
+                err = 0.f;
+                dir = 1;
+                goto direction;
+            }
+        } else {
+            bk_x = nxt_x; bk_y = nxt_y;
+            float dx = bk_x - A.pts[2 * pt];
+            const float dy = bk_y - A.pts[2 * pt + 1];
+            if (WRAP) {  // the short way round
+                const float half = Wf * 0.5f;
+                if (dx > half) dx -= Wf;
+                else if (dx < -half) dx += Wf;
+            }
+            const float d2 = dx * dx + dy * dy;
+            const bool pass = status && d2 <= A.fb_max_dist * A.fb_max_dist;  // (a NaN fails)
+            fb_state = !status ? LK_FB_BACK_LOST : pass ? LK_FB_PASS : LK_FB_TOO_FAR;
+            fb_d2 = status ? d2 : 0.f;
+            nxt_x = fw_x; nxt_y = fw_y; err = fw_err;
+            status = pass;
+        }
+    }
     if (tid == 0) {
         A.next[2 * pt] = nxt_x;
         A.next[2 * pt + 1] = nxt_y;
@@ -548,6 +604,14 @@ __global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
     }
     // the tracked point's bearing (RANSAC's input, FeatureTracker.cpp:262-271) by another wave, beside the stores
     if (A.bear1 && tid == 64) pixel_to_bearing(nxt_x, nxt_y, A.lv[0].w, A.lv[0].h, A.bear1 + 3 * pt);
+    if constexpr (FB) {
+        if (tid == 192) {
+            A.back[2 * pt] = bk_x;
+            A.back[2 * pt + 1] = bk_y;
+            A.fb_state[pt] = (uint8_t)fb_state;
+            A.fb_d2[pt] = fb_d2;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2394,7 +2458,14 @@ hipError_t launch_lk(const LkArgs& a, hipStream_t st, const LkAux* aux) {
     if (aux) x = *aux;
     const int n = a.n > 0 ? a.n : 0, blocks = n + (aux ? LK_AUX_BLOCKS : 0);
     if (blocks == 0) return hipSuccess;
-    if (a.guided != LK_GUESS_NONE) {
+    if (a.fb) {
+        const dim3 g(blocks), b(LK_THREADS);
+        if (a.guided != LK_GUESS_NONE) {
+            if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, true, true>), g, b, 0, st, a, x);
+            else hipLaunchKernelGGL((lk_kernel<false, true, true>), g, b, 0, st, a, x);
+        } else if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, false, true>), g, b, 0, st, a, x);
+        else hipLaunchKernelGGL((lk_kernel<false, false, true>), g, b, 0, st, a, x);
+    } else if (a.guided != LK_GUESS_NONE) {
         if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, true>), dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
         else hipLaunchKernelGGL((lk_kernel<false, true>), dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
     } else if (a.x_wrap) hipLaunchKernelGGL(lk_kernel<true>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);

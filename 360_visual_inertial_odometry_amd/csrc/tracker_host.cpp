@@ -166,6 +166,9 @@ static int tracker_alloc(erp_tracker* t) {
     if ((rc = dalloc(t, &t->d_err, sizeof(float) * P))) return rc;
     if ((rc = dalloc(t, &t->d_guess, sizeof(float) * 2 * P))) return rc;
     if ((rc = dalloc(t, &t->d_guess_out, sizeof(float) * 2 * P))) return rc;
+    if ((rc = dalloc(t, &t->d_back, sizeof(float) * 2 * P))) return rc;
+    if ((rc = dalloc(t, &t->d_fb_d2, sizeof(float) * P))) return rc;
+    if ((rc = dalloc(t, &t->d_fb_state, P))) return rc;
     if ((rc = dalloc(t, &t->d_status, P))) return rc;
     if ((rc = dalloc(t, &t->d_kept, P))) return rc;
     if ((rc = dalloc(t, &t->d_gidx, sizeof(int) * P))) return rc;
@@ -267,6 +270,14 @@ int enqueue_lk(erp_tracker* t, const erp_klt_params* p, int n, bool pyr_built, c
     }
     t->guess_out_valid = a.guided != LK_GUESS_NONE;
     t->pred = LK_GUESS_NONE;
+    a.fb = t->fb.mode;
+    if (a.fb != VIO_FB_OFF) {
+        a.fb_max_dist = t->fb.max_dist;
+        a.back = t->d_back;
+        a.fb_state = t->d_fb_state;
+        a.fb_d2 = t->d_fb_d2;
+    }
+    t->fb_valid = a.fb != VIO_FB_OFF;
     if (t->ev[1] && (!aux || t->stage_timing)) (void)hipEventRecord(t->ev[1], t->ctx->stream);
     hipError_t e = launch_lk(a, t->ctx->stream, aux);
     if (e != hipSuccess) return hip_fail(t->ctx, e, "lk_kernel");
@@ -557,6 +568,15 @@ int tracker_set_rotation(erp_tracker* t, const float R[9], const char* who) {
     return VIO_OK;
 }
 
+int fb_params_ok(vio_ctx* ctx, const erp_fb_params* fb, const char* who) {
+    if (erp_fb_check(fb) != VIO_OK) {
+        set_error(ctx, std::string(who) + (fb ? ": bad erp_fb_params (mode VIO_FB_OFF / VIO_FB_ON, max_dist finite and >= 0)"
+                                              : ": null erp_fb_params"));
+        return VIO_EINVAL;
+    }
+    return VIO_OK;
+}
+
 int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who) {
     if (seam != VIO_SEAM_CUT && seam != VIO_SEAM_WRAP) {
         set_error(ctx, std::string(who) + ": unknown seam mode");
@@ -703,6 +723,29 @@ int erp_tracker_download_guess(erp_tracker* t, float* guess) {
     VIO_HIP(t->ctx, hipStreamSynchronize(t->ctx->stream));
     if (t->n_pts)
         VIO_HIP(t->ctx, hipMemcpy(guess, t->d_guess_out, sizeof(float) * 2 * t->n_pts, hipMemcpyDeviceToHost));
+    return VIO_OK;
+}
+
+int erp_tracker_set_fb(erp_tracker* t, const erp_fb_params* fb) {
+    if (!t) return VIO_EINVAL;
+    const int rc = fb_params_ok(t->ctx, fb, "erp_tracker_set_fb");
+    if (rc) return rc;
+    t->fb = *fb;
+    return VIO_OK;
+}
+
+int erp_tracker_download_fb(erp_tracker* t, float* back, uint8_t* fb_state, float* fb_d2) {
+    if (!t) return VIO_EINVAL;
+    if (!t->fb_valid) {
+        set_error(t->ctx, "erp_tracker_download_fb: the last run had the round-trip check off");
+        return VIO_EINVAL;
+    }
+    VIO_DEVICE(t->ctx);
+    VIO_HIP(t->ctx, hipStreamSynchronize(t->ctx->stream));
+    const int n = t->n_pts;
+    if (n && back) VIO_HIP(t->ctx, hipMemcpy(back, t->d_back, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+    if (n && fb_state) VIO_HIP(t->ctx, hipMemcpy(fb_state, t->d_fb_state, n, hipMemcpyDeviceToHost));
+    if (n && fb_d2) VIO_HIP(t->ctx, hipMemcpy(fb_d2, t->d_fb_d2, sizeof(float) * n, hipMemcpyDeviceToHost));
     return VIO_OK;
 }
 
@@ -875,6 +918,13 @@ int erp_tracker_stage_ms(erp_tracker* t, double* pyr_ms, double* lk_ms, double* 
     return VIO_OK;
 }
 
+int erp_fb_check(const erp_fb_params* fb) {
+    if (!fb || (fb->mode != VIO_FB_OFF && fb->mode != VIO_FB_ON) || !std::isfinite(fb->max_dist) ||
+        !(fb->max_dist >= 0.f))
+        return VIO_EINVAL;
+    return VIO_OK;
+}
+
 int erp_seam_check(int W, int H, int win, int max_level, double min_dist) {
     if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || win <= 2 || win > LK_WIN_MAX || max_level < 0 ||
         max_level >= TRK_MAX_LEVELS || !(min_dist >= 0))
@@ -894,13 +944,21 @@ int erp_klt_track(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W,
 }
 
 // the one-shot LK calls: a tracker for the call, the two frames, the points, one LK launch.  guess / R: the guided
-// forms (at most one of them); guess_out: the start positions used (guided only, may be null)
+// forms (at most one of them); guess_out: the start positions used (guided only, may be null); fb: the round-trip
+// check (null: off) and where its three arrays go (each may be null)
+struct FbOut {
+    const erp_fb_params* fb;
+    float* back;
+    uint8_t* state;
+    float* d2;
+};
 static int klt_track_once(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
                           const float* pts, int n, float* next, uint8_t* status, float* err,
                           const erp_klt_params* params, int seam, const float* guess, const float* R,
-                          float* guess_out, const char* who) {
+                          float* guess_out, const char* who, const FbOut* fbo = nullptr) {
     int rc = check_klt(ctx, params);
     if (rc) return rc;
+    if (fbo && (rc = fb_params_ok(ctx, fbo->fb, who))) return rc;
     if ((rc = seam_mode_ok(ctx, seam, W, H, params->win, params->max_level, 0.0, who))) return rc;
     if (R && !is_rotation(R)) {
         set_error(ctx, std::string(who) + ": R_cur_prev is not a rotation");
@@ -910,6 +968,8 @@ static int klt_track_once(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr
     erp_tracker* t = nullptr;
     if ((rc = erp_tracker_create(ctx, W, H, std::max(n, 1), 0, &t))) return rc;
     t->seam = seam;
+    const bool fb_on = fbo && fbo->fb->mode != VIO_FB_OFF;
+    if (fbo) t->fb = *fbo->fb;
     if (!(rc = upload_frame(t, 0, prev, stride)) && !(rc = upload_frame(t, 1, curr, stride)) &&
         !(rc = erp_tracker_set_points(t, pts, n)) && !(rc = guess ? erp_tracker_set_guess(t, guess, n) : VIO_OK) &&
         !(rc = R ? tracker_set_rotation(t, R, who) : VIO_OK) && !(rc = enqueue_lk(t, params, n))) {
@@ -920,7 +980,12 @@ static int klt_track_once(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr
                 hipMemcpy(status, t->d_status, n, hipMemcpyDeviceToHost) != hipSuccess ||
                 (err && hipMemcpy(err, t->d_err, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
                 (guess_out &&
-                 hipMemcpy(guess_out, t->d_guess_out, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess))
+                 hipMemcpy(guess_out, t->d_guess_out, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (fb_on && fbo->back &&
+                 hipMemcpy(fbo->back, t->d_back, sizeof(float) * 2 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (fb_on && fbo->state && hipMemcpy(fbo->state, t->d_fb_state, n, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (fb_on && fbo->d2 &&
+                 hipMemcpy(fbo->d2, t->d_fb_d2, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess))
                 rc = hip_fail(ctx, hipErrorUnknown, "erp_klt_track download");
         }
     }
@@ -958,6 +1023,20 @@ int erp_klt_track_rot(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, in
     }
     return klt_track_once(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, seam, nullptr, R_cur_prev,
                           guess_out, "erp_klt_track_rot");
+}
+
+int erp_klt_track_fb(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                     const float* pts, const float* guess, int n, float* next, uint8_t* status, float* err,
+                     float* back, uint8_t* fb_state, float* fb_d2, const erp_klt_params* params, int seam,
+                     const erp_fb_params* fb) {
+    if (!ctx) return VIO_EINVAL;
+    if (!prev || !curr || n < 0 || (n > 0 && (!pts || !next || !status))) {
+        set_error(ctx, "erp_klt_track_fb: null frame, points or output, or n < 0");
+        return VIO_EINVAL;
+    }
+    const FbOut fbo{fb, back, fb_state, fb_d2};
+    return klt_track_once(ctx, prev, curr, W, H, stride, pts, n, next, status, err, params, seam, guess, nullptr,
+                          nullptr, "erp_klt_track_fb", &fbo);
 }
 
 int erp_predict_from_preint(const vio_preint* pre, const float* T_BC, float R_cur_prev[9]) {

@@ -82,6 +82,12 @@ struct erp_tracker {
     float pred_rot[9] = {};
     float *d_guess = nullptr, *d_guess_out = nullptr;  // [max_points][2]: explicit guesses / start positions used
     bool guess_out_valid = false;                      // the last LK launch was guided and wrote d_guess_out
+    // round-trip check (erp_tracker_set_fb): persistent like the seam mode; enqueue_lk takes the FB instance while
+    // it is on, so the pipeline and the front end follow it
+    erp_fb_params fb{VIO_FB_OFF, 0.5f};
+    float *d_back = nullptr, *d_fb_d2 = nullptr;  // [max_points][2] / [max_points]
+    uint8_t* d_fb_state = nullptr;                // [max_points] VIO_FB_*
+    bool fb_valid = false;                        // the last LK launch ran the check and wrote the three
     // GFTT top-K fast path
     unsigned int* d_hist = nullptr;
     unsigned long long *d_topk = nullptr, *d_topk_sorted = nullptr;
@@ -119,6 +125,8 @@ int ensure_halfw(erp_tracker* t, int radius);
 bool is_rotation(const float R[9]);
 // the tracker's next LK launch starts every point at BearingToPixel(R_cur_prev * PixelToBearing(prev))
 int tracker_set_rotation(erp_tracker* t, const float R_cur_prev[9], const char* who);
+// erp_fb_check with the caller's name in the context's error
+int fb_params_ok(vio_ctx* ctx, const erp_fb_params* fb, const char* who);
 int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who);
 // Brings the frame into slot `slot` as the tracker's W x H grey image, all on the context stream.
 int tracker_ingest(erp_tracker* t, int slot, const FrameSrc& f, const char* who);

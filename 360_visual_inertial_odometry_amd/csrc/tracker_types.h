@@ -49,8 +49,17 @@ struct LkArgs {
     const float* guess;  // [n][2] (LK_GUESS_PTS)
     float rot[9];        // R_cur_prev, row-major (LK_GUESS_ROT)
     float* guess_out;    // [n][2] or null: the start position each point actually used
+    // round-trip check (the FB instances of lk_kernel, launched when fb != 0): a found point is tracked back from
+    // its next position into the previous frame, guess = its previous position, and passes when it lands within
+    // fb_max_dist of it; status = forward AND pass
+    int fb;
+    float fb_max_dist;  // pixels; the test is d2 <= fb_max_dist * fb_max_dist in f32
+    float* back;        // [n][2] where the backward search ended; (0, 0) where it was not run
+    uint8_t* fb_state;  // [n] LK_FB_*
+    float* fb_d2;       // [n] squared distance of back from pts; 0 where not run or the backward search lost it
 };
 constexpr int LK_GUESS_NONE = 0, LK_GUESS_PTS = 1, LK_GUESS_ROT = 2;
+constexpr int LK_FB_NOT_RUN = 0, LK_FB_PASS = 1, LK_FB_BACK_LOST = 2, LK_FB_TOO_FAR = 3;  // = VIO_FB_* (vio360.h)
 
 struct RansacArgs {
     const float* p0;       // [n][2] previous points

@@ -1024,6 +1024,53 @@ int erp_frontend_predict_rotation(erp_frontend* f, const float R_cur_prev[9]);
    block is not a rotation (the test above). */
 int erp_predict_from_preint(const vio_preint* between_frames, const float* T_BC, float R_cur_prev[9]);
 
+/* Round-trip check (forward-backward LK; VINS-Fusion's FLOW_BACK): status == 1 only says that the
+   window stayed in the frame and was textured.  With the check on, a found point is tracked back into the previous
+   frame and kept only if it lands where it started.  Off by default; with it off every entry point is bit for bit
+   what it is without this section.  With it on, for every point, inside the point's one LK workgroup:
+     forward    the search the call would make without the check (unguided, explicit guess or rotation, either seam
+                mode); next, err and guess_out are its results, unchanged.  In VIO_SEAM_WRAP next.x is folded first,
+                and a point the fold declares lost counts as forward-lost.
+     backward   only for points the forward search found:
+                cv::calcOpticalFlowPyrLK(curr, prev, next, back, ..., OPTFLOW_USE_INITIAL_FLOW) with back = pts --
+                the template and Scharr derivatives from curr's pyramid at next, the search window from prev's, the
+                guess the point's previous position under the guided search's rules (the bad-guess rule, the fold in
+                WRAP), the erp_klt_params and the seam mode of the forward search.  It is
+                erp_klt_track_guess(curr, prev, next, guess = pts) on the forward-found subset, bit for bit.
+     test       f32, no contraction: dx = back.x - pts.x, dy = back.y - pts.y; in WRAP the short way round
+                (dx > W/2: dx -= W; dx < -W/2: dx += W; W/2 = (float)W * 0.5f); d2 = dx*dx + dy*dy.  The point
+                passes iff the backward status is 1 and d2 <= max_dist * max_dist (an f32 product); a NaN fails.
+     results    status = forward AND pass.  fb_state: VIO_FB_NOT_RUN (forward lost), VIO_FB_PASS, VIO_FB_BACK_LOST,
+                VIO_FB_TOO_FAR.  back is (0, 0) where the backward search was not run, and where it was run what
+                that search returned.  fb_d2 is d2 in squared pixels (no square root: bit-defined), 0 where the
+                search was not run or lost the point.  Everything downstream (filter, RANSAC, discs, the front end's
+                feature list) sees only status.
+   erp_fb_check (host only) is the check every entry point makes before anything is launched: VIO_EINVAL for a null
+   pointer, an unknown mode, or a max_dist that is not finite or is negative. */
+enum { VIO_FB_OFF = 0, VIO_FB_ON = 1 };
+enum { VIO_FB_NOT_RUN = 0, VIO_FB_PASS = 1, VIO_FB_BACK_LOST = 2, VIO_FB_TOO_FAR = 3 };
+typedef struct erp_fb_params {
+    int32_t mode;   /* VIO_FB_OFF / VIO_FB_ON */
+    float max_dist; /* pixels; VINS-Fusion's 0.5 is the usual value */
+} erp_fb_params;
+int erp_fb_check(const erp_fb_params* fb);
+/* one-shot, like erp_klt_track_guess; guess may be NULL (unguided forward search); back[n][2], fb_state[n] and
+   fb_d2[n] may each be NULL.  With fb->mode == VIO_FB_OFF it is the unchecked call and the three are not written. */
+int erp_klt_track_fb(vio_ctx* ctx, const uint8_t* prev, const uint8_t* curr, int W, int H, int stride,
+                     const float* pts, const float* guess, int n, float* next, uint8_t* status, float* err,
+                     float* back, uint8_t* fb_state, float* fb_d2, const erp_klt_params* params, int seam,
+                     const erp_fb_params* fb);
+/* device pipeline: persistent, like erp_tracker_set_seam; erp_tracker_run's LK stage follows it, and composes with
+   erp_tracker_set_guess / erp_tracker_set_rotation (which stay one-shot), the seam mode, masks and equalisation */
+int erp_tracker_set_fb(erp_tracker* t, const erp_fb_params* fb);
+/* the last run's back[n][2], fb_state[n], fb_d2[n] (each may be NULL); VIO_EINVAL when that run had the check off */
+int erp_tracker_download_fb(erp_tracker* t, float* back, uint8_t* fb_state, float* fb_d2);
+/* front end: from the next frame on */
+int erp_frontend_set_fb(erp_frontend* f, const erp_fb_params* fb);
+/* the check's counts in the last erp_frontend_track* call: points tracked back, of them lost on the way back, of
+   them landed too far (each may be NULL); all zero when that call ran no LK or the check was off */
+int erp_frontend_fb_stats(erp_frontend* f, int* checked, int* back_lost, int* too_far);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

@@ -16,7 +16,8 @@ from .abi import (VIO_BA_FULL, VIO_BA_LOCAL, VIO_BA_VI, VIO_PNP, VIO_SEAM_CUT, V
                   ErpFrontendParams, ErpKltParams, ErpTrackerParams, default_frontend_params,
                   default_klt_params, default_tracker_params,
                   VIO_FB_OFF, VIO_FB_ON, VIO_FB_NOT_RUN, VIO_FB_PASS, VIO_FB_BACK_LOST, VIO_FB_TOO_FAR,
-                  ErpFbParams, default_fb_params)
+                  ErpFbParams, default_fb_params,
+                  VIO_EPI_OFF, VIO_EPI_ON, ErpEpiParams, ErpEpiInfo, default_epi_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIO360_LIB") or os.path.join(_HERE, "libvio360.so")
@@ -69,6 +70,8 @@ EXPORTS = [
     "erp_tracker_download_guess", "erp_frontend_predict_rotation", "erp_predict_from_preint",
     "erp_fb_check", "erp_klt_track_fb", "erp_tracker_set_fb", "erp_tracker_download_fb", "erp_frontend_set_fb",
     "erp_frontend_fb_stats",
+    "erp_epi_check", "erp_epi_ransac", "erp_tracker_set_epipolar", "erp_tracker_download_epi",
+    "erp_frontend_set_epipolar", "erp_frontend_epi_stats",
     "vio_ba_record_bytes", "vio_ba_batch_record_bytes", "vio_ba_batch_pack", "vio_ba_record_unpack",
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
@@ -229,6 +232,15 @@ def lib():
         L.erp_tracker_download_fb.argtypes = [vp, vp, vp, vp]
         L.erp_frontend_set_fb.argtypes = [vp, fbp]
         L.erp_frontend_fb_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "erp_epi_check") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        epp, epi = C.POINTER(abi.ErpEpiParams), C.POINTER(abi.ErpEpiInfo)
+        L.erp_epi_check.argtypes = [epp]
+        L.erp_epi_ransac.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, epp, vp,
+                                     C.POINTER(C.c_int), vp, epi]
+        L.erp_tracker_set_epipolar.argtypes = [vp, epp]
+        L.erp_tracker_download_epi.argtypes = [vp, epi]
+        L.erp_frontend_set_epipolar.argtypes = [vp, epp]
+        L.erp_frontend_epi_stats.argtypes = [vp, epi]
     L.vio_ba_record_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     L.vio_ba_record_bytes.restype = C.c_size_t
     L.vio_ba_batch_record_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -651,6 +663,24 @@ class Context:
         self.check(lib().erp_rot_ransac(self.h, _p(p0), _p(p1), n, W, H, _p(samples), len(samples) // 3,
                                         float(thr), _p(mask), C.byref(nin)), "erp_rot_ransac")
         return mask, nin.value
+
+    def epi_ransac(self, p0, p1, W, H, samples, R=None, params=None):
+        """erp_epi_ransac: known-rotation epipolar RANSAC on an injected sample stream (rows of three indices, the
+        first two make a hypothesis).  R (3x3, R_cur_prev) or None: the rotation RANSAC's best over the same rows.
+        -> (mask u8, n_inliers, counts (iters,) int32, info dict: n_rot, n_rescued, best, model_valid, t_dir)."""
+        p0 = np.ascontiguousarray(p0, np.float32).reshape(-1, 2)
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        samples = np.ascontiguousarray(samples, np.int32).reshape(-1)
+        n, iters = len(p0), len(samples) // 3
+        prm = params if params is not None else default_epi_params(VIO_EPI_ON)
+        Rf = None if R is None else np.ascontiguousarray(R, np.float32).reshape(9)
+        mask = np.zeros(max(n, 1), np.uint8)
+        counts = np.zeros(max(iters, 1), np.int32)
+        nin, info = C.c_int(), abi.ErpEpiInfo()
+        self.check(lib().erp_epi_ransac(self.h, _p(p0), _p(p1), n, W, H, _p(Rf) if Rf is not None else None,
+                                        _p(samples), iters, C.byref(prm), _p(mask), C.byref(nin), _p(counts),
+                                        C.byref(info)), "erp_epi_ransac")
+        return mask[:n], nin.value, counts[:iters], abi.epi_info_dict(info)
 
 
 def load_camera_timestamps(path):
@@ -1130,6 +1160,16 @@ class Tracker:
         self.ctx.check(lib().erp_tracker_download_fb(self.h, _p(back), _p(state), _p(d2)), "erp_tracker_download_fb")
         return back[:self.n], state[:self.n], d2[:self.n]
 
+    def set_epipolar(self, params):
+        """erp_tracker_set_epipolar: the epipolar stage (ErpEpiParams) of every later run, until set again."""
+        self.ctx.check(lib().erp_tracker_set_epipolar(self.h, C.byref(params)), "erp_tracker_set_epipolar")
+
+    def download_epi(self):
+        """erp_tracker_download_epi: the last run's stage info (dict); raises when that run had the mode off."""
+        info = abi.ErpEpiInfo()
+        self.ctx.check(lib().erp_tracker_download_epi(self.h, C.byref(info)), "erp_tracker_download_epi")
+        return abi.epi_info_dict(info)
+
     def download_guess(self):
         """erp_tracker_download_guess: the start positions the last (guided) run used, (n, 2) float32."""
         g = np.zeros((max(self.n, 1), 2), np.float32)
@@ -1227,6 +1267,16 @@ class Frontend:
         self.ctx.check(lib().erp_frontend_fb_stats(self.h, C.byref(a), C.byref(b), C.byref(c)),
                        "erp_frontend_fb_stats")
         return a.value, b.value, c.value
+
+    def set_epipolar(self, params):
+        """erp_frontend_set_epipolar: the epipolar stage (ErpEpiParams) in RANSAC's place, from the next frame on."""
+        self.ctx.check(lib().erp_frontend_set_epipolar(self.h, C.byref(params)), "erp_frontend_set_epipolar")
+
+    def epi_stats(self):
+        """erp_frontend_epi_stats: the stage's info (dict) in the last track call."""
+        info = abi.ErpEpiInfo()
+        self.ctx.check(lib().erp_frontend_epi_stats(self.h, C.byref(info)), "erp_frontend_epi_stats")
+        return abi.epi_info_dict(info)
 
     def predict_rotation(self, R_cur_prev):
         """erp_frontend_predict_rotation: the next track* call's LK starts where R_cur_prev (3x3, e.g. from

@@ -111,6 +111,35 @@ def default_fb_params(max_dist=0.5):
     return ErpFbParams(VIO_FB_ON, max_dist)
 
 
+class ErpEpiParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("iters", C.c_int32), ("epi_thresh_rad", C.c_float),
+                ("rot_thresh_rad", C.c_float), ("max_parallax_rad", C.c_float), ("min_plane_angle_rad", C.c_float),
+                ("min_support", C.c_int32)]
+
+
+class ErpEpiInfo(C.Structure):
+    _fields_ = [("n_rot", C.c_int32), ("n_rescued", C.c_int32), ("best", C.c_int32), ("model_valid", C.c_int32),
+                ("t_dir", C.c_float * 3)]
+
+
+VIO_EPI_OFF, VIO_EPI_ON = 0, 1
+
+
+def _deg(d):
+    return float(np.float32(np.float64(np.float32(d)) * np.pi / np.float64(np.float32(180.0))))
+
+
+def default_epi_params(mode=VIO_EPI_OFF):
+    """the known-rotation epipolar RANSAC's defaults: 256 hypotheses, 0.25 deg to the epipolar plane, the rotation
+    test's 2 deg, at most 20 deg of parallax, sample planes at least 1 deg apart, 10 rescued tracks for a model"""
+    return ErpEpiParams(mode, 256, _deg(0.25), _deg(2.0), _deg(20.0), _deg(1.0), 10)
+
+
+def epi_info_dict(info):
+    return {"n_rot": info.n_rot, "n_rescued": info.n_rescued, "best": info.best, "model_valid": info.model_valid,
+            "t_dir": np.array(list(info.t_dir), np.float32)}
+
+
 def default_frontend_params(seed=0):
     """config/default_config.yaml values the tracker reads (feature_detection.*, camera.boundary_margin,
     visualization.highlight_clustered_grid / clustered_std_ratio)."""

@@ -99,6 +99,8 @@ struct erp_frontend {
     // erp_frontend_fb_stats: the round-trip check's counts in the last track call (zero when it ran no LK, or
     // the check was off)
     int fb_checked = 0, fb_back_lost = 0, fb_too_far = 0;
+    erp_epi_params epi{};  // erp_frontend_set_epipolar; mode VIO_EPI_OFF: today's rotation RANSAC alone
+    erp_epi_info epi_info{0, 0, -1, 0, {0.f, 0.f, 0.f}};  // erp_frontend_epi_stats: the stage in the last track call
 };
 
 namespace {
@@ -148,6 +150,7 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
     const bool predicted = f->has_pred;  // this call's prediction, consumed whatever the call does
     f->has_pred = false;
     f->fb_checked = f->fb_back_lost = f->fb_too_far = 0;
+    f->epi_info = erp_epi_info{0, 0, -1, 0, {0.f, 0.f, 0.f}};
     if (f->eq.mode != VIO_EQ_NONE && (rc = erp_tracker_equalize(t, 1, &f->eq))) return rc;
     if (f->frame == 0 || f->feats.empty()) {
         // first frame (or nothing to track): detect only (:68-97)
@@ -198,7 +201,35 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
             if (status[i] && !polar && !nearb && (usable.empty() || usable[i])) good.push_back(i);
         }
         std::vector<uint8_t> inl(good.size(), 1);
-        if (good.size() >= 3) {  // RejectOutliersRotationRANSAC (:253-328)
+        const bool epi = f->epi.mode != VIO_EPI_OFF;
+        const bool given = epi && predicted;  // the stage's rotation is this call's prediction
+        if (epi && (good.size() >= 3 || (given && !good.empty()))) {
+            // the epipolar stage in RANSAC's place: the rotation hypotheses (unless a rotation was predicted), then
+            // the plane hypotheses on the first rows of the same sample stream
+            const int ng = (int)good.size();
+            const int rot_iters = given ? 0 : 1000, epi_iters = ng >= 3 ? f->epi.iters : 0;
+            const int ns = ng >= 3 ? std::max(rot_iters, epi_iters) : 0;
+            std::vector<int32_t> samples(3 * (size_t)std::max(ns, 1));
+            if (ns) erp_ransac_samples(P.ransac_seed + (uint32_t)f->frame, ng, ns, samples.data());
+            if ((rc = ensure_iters(t, std::max(ns, 1))) || (rc = ensure_epi(t))) return rc;
+            std::vector<float> g0(2 * (size_t)ng), g1(2 * (size_t)ng);
+            for (int j = 0; j < ng; ++j) {
+                g0[2 * j] = prev[2 * good[j]]; g0[2 * j + 1] = prev[2 * good[j] + 1];
+                g1[2 * j] = next[2 * good[j]]; g1[2 * j + 1] = next[2 * good[j] + 1];
+            }
+            VIO_HIP(ctx, hipMemcpyAsync(t->d_pts, g0.data(), sizeof(float) * 2 * ng, hipMemcpyHostToDevice, st));
+            VIO_HIP(ctx, hipMemcpyAsync(t->d_next, g1.data(), sizeof(float) * 2 * ng, hipMemcpyHostToDevice, st));
+            if (ns)
+                VIO_HIP(ctx, hipMemcpyAsync(t->d_samples, samples.data(), sizeof(int32_t) * 3 * ns, hipMemcpyHostToDevice, st));
+            RansacArgs r = ransac_args(t, ng, 0, ng >= 3 ? rot_iters : 0, 0, f->epi.rot_thresh_rad, 0.f, 0, t->d_pts,
+                                       t->d_next);
+            hipError_t e = launch_ransac_parts(r, false, !given, st);
+            if (e == hipSuccess)
+                e = launch_epipolar(epi_args(t, r, f->epi, epi_iters, 3, given ? f->pred_rot : nullptr), st);
+            if (e != hipSuccess) return hip_fail(ctx, e, "epipolar kernels");
+            VIO_HIP(ctx, hipMemcpyAsync(inl.data(), t->d_kept, ng, hipMemcpyDeviceToHost, st));
+            if ((rc = epi_read_info(t, &f->epi_info))) return rc;
+        } else if (good.size() >= 3) {  // RejectOutliersRotationRANSAC (:253-328)
             const int ng = (int)good.size();
             std::vector<int32_t> samples(3 * 1000);
             erp_ransac_samples(P.ransac_seed + (uint32_t)f->frame, ng, 1000, samples.data());
@@ -322,6 +353,20 @@ int erp_frontend_set_fb(erp_frontend* f, const erp_fb_params* fb) {
     if (!f) return VIO_EINVAL;
     const int rc = fb_params_ok(f->t->ctx, fb, "erp_frontend_set_fb");
     return rc ? rc : erp_tracker_set_fb(f->t, fb);
+}
+
+int erp_frontend_set_epipolar(erp_frontend* f, const erp_epi_params* params) {
+    if (!f) return VIO_EINVAL;
+    const int rc = epi_params_ok(f->t->ctx, params, "erp_frontend_set_epipolar");
+    if (rc) return rc;
+    f->epi = *params;
+    return VIO_OK;
+}
+
+int erp_frontend_epi_stats(erp_frontend* f, erp_epi_info* info) {
+    if (!f || !info) return VIO_EINVAL;
+    *info = f->epi_info;
+    return VIO_OK;
 }
 
 int erp_frontend_fb_stats(erp_frontend* f, int* checked, int* back_lost, int* too_far) {

@@ -2488,6 +2488,16 @@ hipError_t launch_ransac(const RansacArgs& r, bool gen_samples, hipStream_t st) 
     hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(256), 0, st, r);
     return hipGetLastError();
 }
+hipError_t launch_ransac_parts(const RansacArgs& r, bool stream, bool rot, hipStream_t st) {
+    if (!stream) hipLaunchKernelGGL(ransac_prep_kernel, dim3(1), dim3(RP_THREADS), 0, st, r);
+    else if (r.x_wrap) hipLaunchKernelGGL((ransac_sample_kernel<true, true>), dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
+    else hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
+    if (rot) {
+        if (r.iters > 0) hipLaunchKernelGGL(ransac_hyp_kernel, dim3((r.iters + 3) / 4), dim3(256), 0, st, r);
+        hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(256), 0, st, r);
+    }
+    return hipGetLastError();
+}
 hipError_t launch_ransac_pipeline(const RansacArgs& r, const DiscArgs& d, hipStream_t st) {
     if (r.x_wrap) hipLaunchKernelGGL((ransac_sample_kernel<true, true>), dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
     else hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);

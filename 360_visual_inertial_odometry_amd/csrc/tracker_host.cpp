@@ -85,6 +85,8 @@ int ensure_iters(erp_tracker* t, int iters) {
     if ((rc = dalloc(t, &t->d_samples, sizeof(int32_t) * 3 * cap)) != VIO_OK) return rc;
     if ((rc = dalloc(t, &t->d_count, sizeof(int) * cap)) != VIO_OK) return rc;
     if ((rc = dalloc(t, &t->d_rot, sizeof(float) * 9 * cap)) != VIO_OK) return rc;
+    if ((rc = dalloc(t, &t->d_epi_count, sizeof(int) * cap)) != VIO_OK) return rc;
+    if ((rc = dalloc(t, &t->d_epi_resc, sizeof(int) * cap)) != VIO_OK) return rc;
     t->iters_cap = cap;
     return VIO_OK;
 }
@@ -577,6 +579,54 @@ int fb_params_ok(vio_ctx* ctx, const erp_fb_params* fb, const char* who) {
     return VIO_OK;
 }
 
+int epi_params_ok(vio_ctx* ctx, const erp_epi_params* p, const char* who) {
+    if (erp_epi_check(p) != VIO_OK) {
+        set_error(ctx, std::string(who) + (p ? ": bad erp_epi_params (mode, iters in [0, 65536], angles in (0, pi/2), "
+                                               "min_support >= 0)"
+                                             : ": null erp_epi_params"));
+        return VIO_EINVAL;
+    }
+    return VIO_OK;
+}
+
+int ensure_epi(erp_tracker* t) {
+    if (t->d_epi_scal) return VIO_OK;
+    int rc;
+    const int P = std::max(t->max_points, 1);
+    if ((rc = dalloc(t, &t->d_epi_pa, sizeof(float4) * P))) return rc;
+    if ((rc = dalloc(t, &t->d_epi_pn, sizeof(float4) * P))) return rc;
+    return dalloc(t, &t->d_epi_scal, sizeof(int) * ES_COUNT);
+}
+
+EpiArgs epi_args(erp_tracker* t, const RansacArgs& r, const erp_epi_params& p, int iters, int min_n, const float* R) {
+    EpiArgs e;
+    std::memset(&e, 0, sizeof e);
+    e.b0 = r.b0; e.b1 = r.b1; e.gidx = r.gidx; e.n_good = r.n_good; e.n_max = r.n;
+    e.samples = r.samples; e.iters = iters; e.min_n = min_n;
+    e.cmin = r.cmin;
+    e.given = R ? 1 : 0;
+    if (R) std::memcpy(e.rot, R, sizeof e.rot);
+    e.rot_count = r.count; e.rot_all = r.rot; e.rot_iters = r.iters;
+    // the thresholds, once, in double, rounded to float: the kernels evaluate no sin / cos
+    const double se = std::sin((double)p.epi_thresh_rad), sp = std::sin((double)p.min_plane_angle_rad);
+    e.s2_epi = (float)(se * se);
+    e.s2_plane = (float)(sp * sp);
+    e.cmax = (float)std::cos((double)p.max_parallax_rad);
+    e.min_support = p.min_support;
+    e.pa = t->d_epi_pa; e.pn = t->d_epi_pn;
+    e.count = t->d_epi_count; e.resc = t->d_epi_resc;
+    e.scal = t->d_epi_scal;
+    e.kept = r.kept; e.n_in = r.n_in;
+    return e;
+}
+
+int epi_read_info(erp_tracker* t, erp_epi_info* info) {
+    static_assert(sizeof(erp_epi_info) == 7 * sizeof(int), "erp_epi_info is the stage's seven scalars");
+    VIO_HIP(t->ctx, hipStreamSynchronize(t->ctx->stream));
+    VIO_HIP(t->ctx, hipMemcpy(info, t->d_epi_scal + ES_INFO, sizeof *info, hipMemcpyDeviceToHost));
+    return VIO_OK;
+}
+
 int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who) {
     if (seam != VIO_SEAM_CUT && seam != VIO_SEAM_WRAP) {
         set_error(ctx, std::string(who) + ": unknown seam mode");
@@ -759,6 +809,14 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
     // GFTT's candidate order is known before the disc mask: the side stream presorts every local maximum after
     // pass 1 and the tail after the hand-off is one greedy pass (Lmax: the masked-maximum tail after the join)
     const bool presel = pl.route == GfRoute::Presel;
+    // epipolar stage: the run's rotation (erp_tracker_set_rotation) before enqueue_lk consumes it; the rotation test
+    // then takes the stage's threshold, so that one cosine bound serves both
+    const bool epi = t->epi.mode != VIO_EPI_OFF;
+    const bool epi_given = epi && t->pred == LK_GUESS_ROT;
+    float epi_rot[9];
+    std::memcpy(epi_rot, t->pred_rot, sizeof epi_rot);
+    const float rot_thresh = epi ? t->epi.rot_thresh_rad : p->ransac_thresh_rad;
+    t->epi_valid = epi;
     // main stream: pyramids, then LK, whose launch also carries the RANSAC draws' raw stream (seed only),
     // the GFTT counters / histogram / top-K reset and the disc bitmap clear in extra workgroups (on the
     // side stream they cost the main stream a cross-stream wait before RANSAC); side stream: GFTT pass 1
@@ -769,7 +827,7 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
         std::memset(&x, 0, sizeof x);
         x.raw = t->d_raw;
         x.seed = p->ransac_seed;
-        x.thresh = p->ransac_thresh_rad;
+        x.thresh = rot_thresh;
         x.cmin = reinterpret_cast<float*>(t->d_scal + TS_CMIN);
         x.hist = t->d_hist;
         x.topk = t->d_topk;
@@ -809,11 +867,22 @@ static int enqueue_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
         VIO_HIP(t->ctx, hipEventRecord(t->join, t->side));
     }
     if (t->stage_timing) VIO_HIP(t->ctx, hipEventRecord(t->ev[2], st));
-    RansacArgs r = ransac_args(t, n, 1, p->ransac_iters, p->ransac_seed, p->ransac_thresh_rad, p->polar_ratio,
-                               p->boundary_margin, t->d_pts, t->d_next);
+    // (with a given rotation no rotation hypothesis is evaluated: the sampler draws the stage's rows only)
+    const int epi_iters = std::min(t->epi.iters, p->ransac_iters);
+    RansacArgs r = ransac_args(t, n, 1, epi_given ? epi_iters : p->ransac_iters, p->ransac_seed, rot_thresh,
+                               p->polar_ratio, p->boundary_margin, t->d_pts, t->d_next);
     r.bear0 = t->d_bear0;  // formed by the LK launch
     r.bear1 = t->d_bear1;
-    if (n > 0) {
+    if (epi) {
+        // the unfused tail: compaction + sampler (+ rotation hypotheses and selection), the epipolar kernels on
+        // kept / TS_N_IN, then the discs around the final kept points
+        DiscArgs d{t->d_next, t->d_kept, nullptr, nullptr, t->d_disc, t->disc_words, t->W, t->H, radius,
+                   t->d_halfw, t->seam};
+        hipError_t e = launch_ransac_parts(r, true, !epi_given, st);
+        if (e == hipSuccess) e = launch_epipolar(epi_args(t, r, t->epi, epi_iters, 3, epi_given ? epi_rot : nullptr), st);
+        if (e == hipSuccess && radius > 0) e = launch_disc_mask(d, n, st);
+        if (e != hipSuccess) return hip_fail(t->ctx, e, "epipolar kernels");
+    } else if (n > 0) {
         // RANSAC, then its selection and CreateFeatureMask's discs of radius (int)min_dist around every kept
         // point in one launch (bitmap cleared in the LK launch; radius 0: no discs)
         DiscArgs d{t->d_next, t->d_kept, nullptr, nullptr, t->d_disc, t->disc_words, t->W, t->H, radius,
@@ -851,6 +920,7 @@ static int tracker_run(erp_tracker* t, const erp_klt_params* klt, const erp_trac
     }
     VIO_DEVICE(t->ctx);
     if ((rc = ensure_iters(t, std::max(p->ransac_iters, 1)))) return rc;
+    if (t->epi.mode != VIO_EPI_OFF && (rc = ensure_epi(t))) return rc;
     const int radius = (int)p->min_dist;  // CreateFeatureMask's discs
     if ((rc = ensure_halfw(t, radius))) return rc;
     GfttPlan plan;
@@ -1130,6 +1200,98 @@ int erp_rot_ransac(vio_ctx* ctx, const float* p0, const float* p1, int n, int W,
     }
     erp_tracker_destroy(t);
     return rc;
+}
+
+// ---- known-rotation epipolar RANSAC (epipolar.hip) ----
+
+int erp_epi_check(const erp_epi_params* p) {
+    if (!p || (p->mode != VIO_EPI_OFF && p->mode != VIO_EPI_ON) || p->iters < 0 || p->iters > kMaxIters ||
+        p->min_support < 0)
+        return VIO_EINVAL;
+    const float half_pi = (float)(M_PI / 2);
+    for (const float a : {p->epi_thresh_rad, p->rot_thresh_rad, p->max_parallax_rad, p->min_plane_angle_rad})
+        if (!(a > 0.f && a < half_pi)) return VIO_EINVAL;  // (a NaN fails both)
+    return VIO_OK;
+}
+
+int erp_epi_ransac(vio_ctx* ctx, const float* p0, const float* p1, int n, int W, int H, const float* R,
+                   const int32_t* samples, int iters, const erp_epi_params* params, uint8_t* mask, int* n_inliers,
+                   int32_t* counts, erp_epi_info* info) {
+    if (!ctx || n < 0 || W <= 0 || H <= 0 || !mask || !n_inliers || !info || iters < 0 || iters > kMaxIters ||
+        (n > 0 && (!p0 || !p1)))
+        return VIO_EINVAL;
+    int rc = epi_params_ok(ctx, params, "erp_epi_ransac");
+    if (rc) return rc;
+    if (R && !is_rotation(R)) { set_error(ctx, "erp_epi_ransac: R is not a rotation"); return VIO_EINVAL; }
+    const int used = R ? 2 : 3;  // indices of a sample row that are read
+    const bool sampled = n >= used && iters > 0;
+    if (sampled && !samples) return VIO_EINVAL;
+    for (int i = 0; counts && i < iters; ++i) counts[i] = -1;
+    std::memset(info, 0, sizeof *info);
+    info->best = -1;
+    if (n == 0 || (!R && n < 3)) {  // no rotation to test against: everything is kept, as erp_rot_ransac does
+        for (int i = 0; i < n; ++i) mask[i] = 1;
+        *n_inliers = info->n_rot = n;
+        return VIO_OK;
+    }
+    for (int it = 0; sampled && it < iters; ++it)
+        for (int s = 0; s < used; ++s)
+            if (samples[3 * it + s] < 0 || samples[3 * it + s] >= n) {
+                set_error(ctx, "erp_epi_ransac: sample index out of range");
+                return VIO_EINVAL;
+            }
+    VIO_DEVICE(ctx);
+    erp_tracker* t = nullptr;
+    rc = erp_tracker_create(ctx, std::max(W, 8), std::max(H, 8), n, 0, &t);
+    if (rc) return rc;
+    t->W = W; t->H = H;
+    float* d_p1 = nullptr;
+    if (!(rc = ensure_iters(t, std::max(iters, 1))) && !(rc = ensure_epi(t)) &&
+        !(rc = dalloc(t, &d_p1, sizeof(float) * 2 * n))) {
+        hipStream_t st = ctx->stream;
+        if (hipMemcpyAsync(t->d_pts, p0, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d_p1, p1, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st) != hipSuccess ||
+            (sampled && hipMemcpyAsync(t->d_samples, samples, sizeof(int32_t) * 3 * iters, hipMemcpyHostToDevice, st) !=
+                            hipSuccess)) {
+            rc = hip_fail(ctx, hipErrorUnknown, "epipolar upload");
+        } else {
+            // (rows that are not read are not uploaded: no hypothesis kernel runs on them)
+            RansacArgs r = ransac_args(t, n, 0, sampled ? iters : 0, 0, params->rot_thresh_rad, 0.f, 0, t->d_pts, d_p1);
+            hipError_t e = R ? launch_ransac_parts(r, false, false, st) : launch_ransac(r, false, st);
+            if (e == hipSuccess) e = launch_epipolar(epi_args(t, r, *params, r.iters, 2, R), st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            int have = 0;
+            if (e != hipSuccess) rc = hip_fail(ctx, e, "epipolar kernels");
+            else if (hipMemcpy(mask, t->d_kept, n, hipMemcpyDeviceToHost) != hipSuccess ||
+                     hipMemcpy(n_inliers, t->d_scal + TS_N_IN, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                     hipMemcpy(&have, t->d_epi_scal + ES_HAVE_R, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                     (counts && have && r.iters > 0 &&
+                      hipMemcpy(counts, t->d_epi_count, sizeof(int) * r.iters, hipMemcpyDeviceToHost) != hipSuccess))
+                rc = hip_fail(ctx, hipErrorUnknown, "epipolar download");
+            else rc = epi_read_info(t, info);
+        }
+    }
+    erp_tracker_destroy(t);
+    return rc;
+}
+
+int erp_tracker_set_epipolar(erp_tracker* t, const erp_epi_params* params) {
+    if (!t) return VIO_EINVAL;
+    const int rc = epi_params_ok(t->ctx, params, "erp_tracker_set_epipolar");
+    if (rc) return rc;
+    t->epi = *params;
+    return VIO_OK;
+}
+
+int erp_tracker_download_epi(erp_tracker* t, erp_epi_info* info) {
+    if (!t) return VIO_EINVAL;
+    if (!info || !t->epi_valid) {
+        set_error(t->ctx, info ? "erp_tracker_download_epi: the last run had the epipolar stage off"
+                               : "erp_tracker_download_epi: null info");
+        return VIO_EINVAL;
+    }
+    VIO_DEVICE(t->ctx);
+    return epi_read_info(t, info);
 }
 
 // ---- seam mode ----

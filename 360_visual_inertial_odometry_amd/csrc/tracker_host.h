@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "epipolar.h"
 #include "tracker_types.h"
 
 namespace vio360 {
@@ -88,6 +89,13 @@ struct erp_tracker {
     float *d_back = nullptr, *d_fb_d2 = nullptr;  // [max_points][2] / [max_points]
     uint8_t* d_fb_state = nullptr;                // [max_points] VIO_FB_*
     bool fb_valid = false;                        // the last LK launch ran the check and wrote the three
+    // epipolar stage (erp_tracker_set_epipolar): persistent like the round-trip check.  Per-point terms and scalars
+    // are allocated on first use (ensure_epi), the per-hypothesis arrays with the others (ensure_iters)
+    erp_epi_params epi{};  // mode VIO_EPI_OFF
+    float4 *d_epi_pa = nullptr, *d_epi_pn = nullptr;  // [max_points]
+    int *d_epi_count = nullptr, *d_epi_resc = nullptr;  // [iters_cap]
+    int* d_epi_scal = nullptr;                          // [ES_COUNT]
+    bool epi_valid = false;                             // the last run had the stage on
     // GFTT top-K fast path
     unsigned int* d_hist = nullptr;
     unsigned long long *d_topk = nullptr, *d_topk_sorted = nullptr;
@@ -127,6 +135,15 @@ bool is_rotation(const float R[9]);
 int tracker_set_rotation(erp_tracker* t, const float R_cur_prev[9], const char* who);
 // erp_fb_check with the caller's name in the context's error
 int fb_params_ok(vio_ctx* ctx, const erp_fb_params* fb, const char* who);
+// erp_epi_check with the caller's name in the context's error
+int epi_params_ok(vio_ctx* ctx, const erp_epi_params* p, const char* who);
+// the stage's buffers (first use)
+int ensure_epi(erp_tracker* t);
+// The stage's arguments behind the compaction / rotation RANSAC described by r: `iters` rows of r.samples, R the
+// given rotation or null (the rotation RANSAC's best over r.iters hypotheses)
+EpiArgs epi_args(erp_tracker* t, const RansacArgs& r, const erp_epi_params& p, int iters, int min_n, const float* R);
+// the stage's info of the last launch (waits for the stream)
+int epi_read_info(erp_tracker* t, erp_epi_info* info);
 int seam_mode_ok(vio_ctx* ctx, int seam, int W, int H, int win, int max_level, double min_dist, const char* who);
 // Brings the frame into slot `slot` as the tracker's W x H grey image, all on the context stream.
 int tracker_ingest(erp_tracker* t, int slot, const FrameSrc& f, const char* who);

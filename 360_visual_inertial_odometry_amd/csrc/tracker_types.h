@@ -230,6 +230,10 @@ hipError_t launch_ransac_raw(uint32_t seed, uint32_t* raw, hipStream_t st);
 size_t ransac_raw_words();
 // gen_samples: hypotheses drawn on device from r.raw (launch_ransac_raw of r.seed must precede)
 hipError_t launch_ransac(const RansacArgs& r, bool gen_samples, hipStream_t st);
+// the epipolar stage's use of the same kernels: the input compaction (stream: the pipeline's sampler with the
+// compaction in front, which draws r.iters rows from r.raw; else the compaction alone, samples uploaded), and with
+// `rot` the rotation hypotheses and the unfused selection
+hipError_t launch_ransac_parts(const RansacArgs& r, bool stream, bool rot, hipStream_t st);
 hipError_t launch_disc_mask(const DiscArgs& d, int max_pts, hipStream_t st);
 // tracker pipeline: sampler (with the input compaction), hypotheses, then selection + discs in one launch
 hipError_t launch_ransac_pipeline(const RansacArgs& r, const DiscArgs& d, hipStream_t st);

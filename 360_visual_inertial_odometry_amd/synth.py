@@ -422,6 +422,28 @@ def rot_yaw_pitch(yaw_deg, pitch_deg):
     return Ry @ Rx
 
 
+def erp_translation_sequence(W, H, frames, step=0.05, yaw_px=0, seed=1):
+    """u8 ERP frames of a static scene seen by a camera that moves `step` per frame along its Y (down) axis and yaws
+    by yaw_px columns per frame.  The scene is a surface of cylindrical radius rho(u) about that axis, textured by
+    render_erp: 1 / rho runs smoothly from 0.1 (far) to 1 (two near pillars half a turn apart).  A point keeps its
+    column and tan(lat) grows by step / rho per frame, so frame k is a per-column vertical remap of the base texture
+    (linear interpolation), rolled by k * yaw_px: X_cur = R X_prev - c with R = rot_yaw_pitch(yaw_px * 360 / W, 0)
+    and c = (0, step, 0) in the camera frame."""
+    base = render_erp(W, H, seed=seed).astype(np.float64)
+    inv_rho = 0.1 + 0.9 * (0.5 + 0.5 * np.cos(4.0 * np.pi * (np.arange(W) + 0.5) / W)) ** 2
+    lat = np.clip(-(np.arange(H) / H - 0.5) * np.pi, -np.pi / 2 + 1e-6, np.pi / 2 - 1e-6)
+    cols = np.arange(W)[None, :]
+    out = []
+    for k in range(frames):
+        lat0 = np.arctan(np.tan(lat)[:, None] - k * step * inv_rho[None, :])  # (H, W): where the texture is read
+        v0 = np.clip((0.5 - lat0 / np.pi) * H, 0.0, H - 1.0)
+        i0 = np.minimum(v0.astype(np.int64), H - 2)
+        f = v0 - i0
+        img = (1.0 - f) * base[i0, cols] + f * base[i0 + 1, cols]
+        out.append(np.roll(np.clip(np.rint(img), 0, 255).astype(np.uint8), k * yaw_px, axis=1))
+    return out
+
+
 def erp_flow_truth(pts, W, H, R_21):
     """Analytic position in frame 2 of frame-1 pixels under a pure rotation: d2 = R_21 d1."""
     pts = np.asarray(pts, np.float64)

@@ -1071,6 +1071,80 @@ int erp_frontend_set_fb(erp_frontend* f, const erp_fb_params* fb);
    them landed too far (each may be NULL); all zero when that call ran no LK or the check was off */
 int erp_frontend_fb_stats(erp_frontend* f, int* checked, int* back_lost, int* too_far);
 
+/* Known-rotation epipolar RANSAC: the rotation test keeps a track when one rotation carries its
+   previous bearing to within rot_thresh of its current one, so under translation it drops every near point.  With
+   the rotation R = R_cur_prev known (the gyro's, or the rotation RANSAC's best), two-view geometry leaves the
+   direction of translation: each track gives one plane through it, two tracks fix it, and every other track is
+   tested against its epipolar plane and the direction of flow.  Off by default; with the mode off every entry
+   point is bit for bit what it is without this section.  The rule, f32 without contraction, sums in the written
+   order:
+     inputs     the n points that pass the stage's input filter, their unit bearings b0[k], b1[k] (PixelToBearing of
+                the previous and the current pixel), R row-major, iters sample rows (i, j, .) of which the first two
+                indices are used, the parameters below.  The thresholds are formed once on the host in double and
+                rounded to float: s2_epi = sin^2(epi_thresh_rad), s2_plane = sin^2(min_plane_angle_rad),
+                cmax = cos(max_parallax_rad); cmin is the rotation test's cosine bound of rot_thresh_rad (the
+                smallest float c with (float)acos((double)c) < rot_thresh_rad).
+     per point  a = R b0 (each row (R0*x + R1*y) + R2*z); c = (a0*q0 + a1*q1) + a2*q2 with q = b1;
+                nrm = a x q = (a1*q2 - a2*q1, a2*q0 - a0*q2, a0*q1 - a1*q0); nn = (nrm0^2 + nrm1^2) + nrm2^2;
+                rin = clamp(c, -1, 1) >= cmin (the rotation test); par_ok = c >= cmax.
+     hypothesis (i, j): skipped (count -1) when rin[i] or rin[j], or when, with t = nrm[i] x nrm[j] and
+                tt = (t0^2 + t1^2) + t2^2, tt >= s2_plane * (nn[i] * nn[j]) does not hold.  Otherwise every point k
+                with !rin[k] and par_ok[k] forms m = t x a[k], mm = (m0^2 + m1^2) + m2^2,
+                e = (t0*nrm0 + t1*nrm1) + t2*nrm2, on_plane = mm > 1e-6f * tt && e * e < s2_epi * mm,
+                s = -((nrm0*m0 + nrm1*m1) + nrm2*m2), and votes pos when on_plane && s > 0, neg when
+                on_plane && s < 0.  rescued = max(pos, neg), sigma = pos >= neg ? +1 : -1,
+                count = (number of rin) + rescued.
+     selection  the first hypothesis with the strictly greatest count >= 0.  When there is none, or its
+                rescued < min_support: mask = rin, model_valid = 0, best = -1 (none) or its index, t_dir = 0.
+                Otherwise mask[k] = rin[k] || (on_plane with the sign sigma) under the best t, model_valid = 1 and
+                t_dir = -sigma * t / sqrtf(tt): the camera's direction of translation in the current camera frame
+                (bearings flow away from it).
+     small n    hypotheses are evaluated from n >= 2 in erp_epi_ransac and from n >= 3 in the tracker and the front
+                end (their sample stream erp_ransac_samples needs three points); below that, and with iters == 0,
+                the result is the rotation mask rin.  Without a given R the rotation RANSAC runs first on the same
+                sample rows (all three indices); when it finds no rotation (n < 3, iters == 0, every hypothesis
+                degenerate) everything is kept as erp_rot_ransac does, n_rot = the count it reports, best = -1.
+   erp_epi_check (host only) is the check every entry point makes before anything is launched: VIO_EINVAL for a null
+   pointer, an unknown mode, a negative or NaN field, iters above 65536 (the tracker's hypothesis cap), or an angle
+   outside (0, pi/2). */
+enum { VIO_EPI_OFF = 0, VIO_EPI_ON = 1 };
+typedef struct erp_epi_params {
+    int32_t mode;              /* VIO_EPI_OFF / VIO_EPI_ON */
+    int32_t iters;             /* hypotheses: the first iters rows of the sample stream (256) */
+    float epi_thresh_rad;      /* angle of b1 to the epipolar plane (0.25 deg) */
+    float rot_thresh_rad;      /* the rotation test's angle (2 deg) */
+    float max_parallax_rad;    /* a rescued track's angle between R b0 and b1 is at most this (20 deg) */
+    float min_plane_angle_rad; /* the two sample planes must differ by at least this (1 deg) */
+    int32_t min_support;       /* a model needs this many rescued tracks (10) */
+} erp_epi_params;
+typedef struct erp_epi_info {
+    int32_t n_rot;       /* tracks the rotation test keeps (rin) */
+    int32_t n_rescued;   /* tracks only the epipolar model keeps (0 when model_valid == 0) */
+    int32_t best;        /* the chosen hypothesis, -1: none */
+    int32_t model_valid; /* 1: the mask is rin || epipolar; 0: the mask is the rotation stage's */
+    float t_dir[3];      /* unit direction of translation, 0 when model_valid == 0 */
+} erp_epi_info;
+int erp_epi_check(const erp_epi_params* params);
+/* one-shot, like erp_rot_ransac: p0, p1 [n][2] pixels, R 9 floats (R_cur_prev) or NULL (the rotation RANSAC's best
+   over `samples`), samples [iters][3] (indices < n; with R given only the first two of a row are read).  Of params,
+   iters (the argument counts) and mode are not looked at.  Outputs: mask[n], *n_inliers, counts[iters] (may be
+   NULL; -1: skipped, or no hypothesis was evaluated), info.  Blocking. */
+int erp_epi_ransac(vio_ctx* ctx, const float* p0, const float* p1, int n, int W, int H, const float* R,
+                   const int32_t* samples, int iters, const erp_epi_params* params, uint8_t* mask, int* n_inliers,
+                   int32_t* counts, erp_epi_info* info);
+/* device pipeline: persistent, like erp_tracker_set_fb.  With the mode on erp_tracker_run's RANSAC stage is followed
+   by the epipolar stage on the first min(iters, ransac_iters) rows of the run's sample stream; R is the rotation of
+   erp_tracker_set_rotation for that run when there is one (the rotation hypotheses are then not evaluated), else
+   the rotation RANSAC's best.  kept, and the discs around kept points, follow the final mask. */
+int erp_tracker_set_epipolar(erp_tracker* t, const erp_epi_params* params);
+/* the last run's info; VIO_EINVAL when that run had the mode off */
+int erp_tracker_download_epi(erp_tracker* t, erp_epi_info* info);
+/* front end: from the next frame on; R is that call's erp_frontend_predict_rotation when one was given, else the
+   rotation RANSAC's best; the sample stream is erp_ransac_samples(ransac_seed + frame, n_good, .) */
+int erp_frontend_set_epipolar(erp_frontend* f, const erp_epi_params* params);
+/* the stage's info in the last erp_frontend_track* call; all zero (best -1) when that call did not run it */
+int erp_frontend_epi_stats(erp_frontend* f, erp_epi_info* info);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Monocular initialisation: Initializer::TryMonocularInitialization           */

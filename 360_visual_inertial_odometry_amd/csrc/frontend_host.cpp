@@ -243,7 +243,7 @@ int frontend_track_slot1(erp_frontend* f, int* n_features) {
             VIO_HIP(ctx, hipMemcpyAsync(t->d_samples, samples.data(), sizeof(int32_t) * 3000, hipMemcpyHostToDevice, st));
             const float thr = (float)(2.0f * M_PI / 180.0f);
             RansacArgs r = ransac_args(t, ng, 0, 1000, 0, thr, 0.f, 0, t->d_pts, t->d_next);
-            hipError_t e = launch_ransac(r, false, st);
+            hipError_t e = launch_ransac_parts(r, false, true, st);
             if (e != hipSuccess) return hip_fail(ctx, e, "ransac kernels");
             VIO_HIP(ctx, hipMemcpyAsync(inl.data(), t->d_kept, ng, hipMemcpyDeviceToHost, st));
             VIO_HIP(ctx, hipStreamSynchronize(st));

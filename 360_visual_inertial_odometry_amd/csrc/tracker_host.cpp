@@ -1,8 +1,8 @@
 // tracker_host.cpp — C-ABI of the ERP feature tracker (erp_*), host side.
 //
 // Owns the device state of a tracker (frame pyramids, point / RANSAC / GFTT buffers) and enqueues
-// the tracker.hip kernels on the context stream.  The standalone entry points erp_klt_track /
-// erp_gftt / erp_rot_ransac mirror the three OpenCV / Eigen calls of FeatureTracker
+// the tracker kernels (trk_lk.hip, trk_ransac.hip, trk_gftt.hip) on the context stream.  The standalone entry
+// points erp_klt_track / erp_gftt / erp_rot_ransac mirror the three OpenCV / Eigen calls of FeatureTracker
 // (src/processing/FeatureTracker.cpp:222-223, 238-240, 253-379); erp_tracker_run chains them for a
 // frame pair without a host round trip.
 #include <hip/hip_runtime.h>
@@ -434,13 +434,13 @@ int enqueue_gftt(erp_tracker* t, const GfttPlan& pl) {
     hipError_t e = pl.pipeline ? hipSuccess : launch_gftt_reset(g, t->d_scal, st);
     if (pl.route == GfRoute::Map) {
         if (e == hipSuccess) e = launch_gftt_eig(g, st);
-        if (e == hipSuccess) e = launch_gftt(g, t->d_sort_tmp, t->sort_tmp_bytes, st);
+        if (e == hipSuccess) e = launch_gftt(g, st);
     } else {
         if (e == hipSuccess && !pl.pipeline) e = launch_gftt_lmax(g, st);
         if (e == hipSuccess)
             e = pl.route == GfRoute::Presel
                     ? launch_gftt_presel(gf_presel_args(t, pl), t->d_topk2_sorted, t->d_hist2 + GF_BUCKETS + PS_N_TOP, st)
-                    : launch_gftt_after_lmax(g, t->d_sort_tmp, t->sort_tmp_bytes, st);
+                    : launch_gftt_after_lmax(g, st);
     }
     if (e != hipSuccess) return hip_fail(t->ctx, e, "gftt kernels");
     return VIO_OK;
@@ -512,14 +512,14 @@ int read_corners(erp_tracker* t, float* out_xy, int* n_out) {
         g.lmax = nullptr;
         hipError_t e = launch_gftt_reset(g, t->d_scal, st);
         if (e == hipSuccess) e = launch_gftt_eig(g, st);
-        if (e == hipSuccess) e = launch_gftt(g, t->d_sort_tmp, t->sort_tmp_bytes, st);
+        if (e == hipSuccess) e = launch_gftt(g, st);
         if (e != hipSuccess) return hip_fail(t->ctx, e, "gftt map path");
         if ((rc = fetch_scalars())) return rc;
     }
     if (pl.resolved == GfRoute::Presel && sc[TS_INCOMPLETE]) {
         // the presorted prefix did not decide (threshold bound reached or prefix exhausted before max_corners):
         // the exact tail -- masked maximum, candidate top-K, greedy pass (its buffers are untouched by presel)
-        hipError_t e = launch_gftt_after_lmax(g, t->d_sort_tmp, t->sort_tmp_bytes, st);
+        hipError_t e = launch_gftt_after_lmax(g, st);
         if (e != hipSuccess) return hip_fail(t->ctx, e, "gftt exact tail");
         pl.resolved = GfRoute::Lmax;
         ++t->n_exact_tail;
@@ -1190,7 +1190,7 @@ int erp_rot_ransac(vio_ctx* ctx, const float* p0, const float* p1, int n, int W,
             rc = hip_fail(ctx, hipErrorUnknown, "ransac upload");
         } else {
             RansacArgs r = ransac_args(t, n, 0, iters, 0, thresh_rad, 0.f, 0, t->d_pts, d_p1);
-            hipError_t e = launch_ransac(r, false, st);
+            hipError_t e = launch_ransac_parts(r, false, true, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) rc = hip_fail(ctx, e, "ransac kernels");
             else if (hipMemcpy(mask, t->d_kept, n, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -1257,7 +1257,7 @@ int erp_epi_ransac(vio_ctx* ctx, const float* p0, const float* p1, int n, int W,
         } else {
             // (rows that are not read are not uploaded: no hypothesis kernel runs on them)
             RansacArgs r = ransac_args(t, n, 0, sampled ? iters : 0, 0, params->rot_thresh_rad, 0.f, 0, t->d_pts, d_p1);
-            hipError_t e = R ? launch_ransac_parts(r, false, false, st) : launch_ransac(r, false, st);
+            hipError_t e = launch_ransac_parts(r, false, !R, st);
             if (e == hipSuccess) e = launch_epipolar(epi_args(t, r, *params, r.iters, 2, R), st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             int have = 0;

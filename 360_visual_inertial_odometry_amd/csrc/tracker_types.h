@@ -1,5 +1,5 @@
-// tracker_types.h — kernel argument blocks of the ERP tracker (tracker.hip), shared with the host
-// side (tracker_host.cpp, frontend_host.cpp).
+// tracker_types.h — kernel argument blocks and launchers of the ERP tracker (trk_lk.hip, trk_ransac.hip,
+// trk_gftt.hip), shared with the host side (tracker_host.cpp, frontend_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,7 +77,7 @@ struct RansacArgs {
     const float* bear0;    // [n][3] or null: every input point's bearings already formed (tracker pipeline: the
     const float* bear1;    // LK launch); the compaction then copies them instead of evaluating the trigonometry
     int32_t* samples;      // [iters][3]
-    const uint32_t* raw;   // [RS_RAW] tempered mt19937 words of `seed` (ransac_raw_kernel)
+    const uint32_t* raw;   // [ransac_raw_words()] tempered mt19937 words of `seed` (lk_aux, LkAux::raw)
     int iters;
     uint32_t seed;
     float thresh;
@@ -225,14 +225,11 @@ struct LkAux {
     int n, W, H;
 };
 hipError_t launch_lk(const LkArgs& a, hipStream_t st, const LkAux* aux = nullptr);
-// the tempered mt19937 stream of a seed (independent of the points: may run on another stream)
-hipError_t launch_ransac_raw(uint32_t seed, uint32_t* raw, hipStream_t st);
-size_t ransac_raw_words();
-// gen_samples: hypotheses drawn on device from r.raw (launch_ransac_raw of r.seed must precede)
-hipError_t launch_ransac(const RansacArgs& r, bool gen_samples, hipStream_t st);
-// the epipolar stage's use of the same kernels: the input compaction (stream: the pipeline's sampler with the
-// compaction in front, which draws r.iters rows from r.raw; else the compaction alone, samples uploaded), and with
-// `rot` the rotation hypotheses and the unfused selection
+size_t ransac_raw_words();  // words of the tempered mt19937 stream of a seed (LkAux::raw, RansacArgs::raw)
+// rotation RANSAC outside the pipeline, and the epipolar stage's use of the same kernels: the input compaction
+// (stream: the pipeline's sampler with the compaction in front, which draws r.iters rows from r.raw, the LK launch's
+// LkAux::raw; else the compaction alone, samples uploaded), and with `rot` the rotation hypotheses and the unfused
+// selection.  (r, false, true): RejectOutliersRotationRANSAC over uploaded samples
 hipError_t launch_ransac_parts(const RansacArgs& r, bool stream, bool rot, hipStream_t st);
 hipError_t launch_disc_mask(const DiscArgs& d, int max_pts, hipStream_t st);
 // tracker pipeline: sampler (with the input compaction), hypotheses, then selection + discs in one launch
@@ -246,13 +243,13 @@ hipError_t launch_gftt_presort(const GfArgs& g, hipStream_t st);
 hipError_t launch_gftt_presel(const GfArgs& g, const unsigned long long* keys, const unsigned int* n_keys,
                               hipStream_t st);
 hipError_t launch_gftt_eig(const GfArgs& g, hipStream_t st);  // the min-eigenvalue map (needs img, W, H, pitch, eig)
-hipError_t launch_gftt(const GfArgs& g, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st);  // after the map
+hipError_t launch_gftt(const GfArgs& g, hipStream_t st);  // after the map
 hipError_t launch_gftt_full(const GfArgs& g, unsigned int count, void* sort_tmp, size_t sort_tmp_bytes,
                             hipStream_t st);  // sorts the first `count` candidates (n_cand read back)
 hipError_t launch_gftt_reset(const GfArgs& g, int* scal, hipStream_t st);
 // local-maximum path: pass 1 (mask independent) and everything after the mask is known
 hipError_t launch_gftt_lmax(const GfArgs& g, hipStream_t st);
-hipError_t launch_gftt_after_lmax(const GfArgs& g, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st);
+hipError_t launch_gftt_after_lmax(const GfArgs& g, hipStream_t st);
 // exact fallback of the local-maximum path: flatten the surviving candidates, then launch_gftt_full
 hipError_t launch_gftt_flatten(const GfArgs& g, hipStream_t st);
 size_t gftt_sort_tmp_bytes(unsigned int cap);

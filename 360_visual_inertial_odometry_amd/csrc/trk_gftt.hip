@@ -1,15 +1,6 @@
-// tracker.hip — ERP feature tracking on MI355X (gfx950): the numeric path of
-// FeatureTracker::TrackFeatures (src/processing/FeatureTracker.cpp:61-379).
+// trk_gftt.hip — ERP feature tracking on MI355X (gfx950), detection: the last stage of
+// FeatureTracker::TrackFeatures (src/processing/FeatureTracker.cpp:61-379), after trk_lk.hip and trk_ransac.hip.
 //
-//   pyr_down_kernel      cv::pyrDown inside buildOpticalFlowPyramid: 5x5 [1 4 6 4 1]^2/256,
-//                        BORDER_REFLECT_101; both frames of a pair in one launch (blockIdx.z).
-//   lk_kernel            cv::calcOpticalFlowPyrLK's LKTrackerInvoker, one wavefront per point,
-//                        all pyramid levels in one launch; the Scharr derivatives of the previous
-//                        frame are computed on the fly from an LDS-staged 24x24 tile (never
-//                        materialised for the whole image), the 21x21 patch, its derivatives and
-//                        every 22x22 next-frame tile live in LDS; gradient/mismatch sums are exact
-//                        int64 wave reductions.
-//   ransac_*             RejectOutliersRotationRANSAC: one wavefront per hypothesis.
 //   gftt_*               cv::goodFeaturesToTrack(blockSize 3, Sobel 3): pass 1 computes the
 //                        min-eigenvalue map on LDS tiles (Sobel, 3x3 box, eigenvalue), writes it
 //                        (f32, W x H) and reduces its masked maximum; pass 2 reads a haloed tile of
@@ -17,1103 +8,22 @@
 //                        (response, address) keys; a top-K histogram cut, a sort and one
 //                        workgroup's greedy min-distance pass finish.  (Recomputing the map in
 //                        pass 2 cost more than its 2 x 4 B/px round trip through HBM / MALL.)
-// Seam wrap mode (VIO_SEAM_WRAP, the x_wrap flag of the argument blocks): every stage on the horizontally periodic
-// continuation of the frame -- wrapped border columns, no sideways exit and no side margins, discs and the
-// min-distance test on the cylinder, detection through the map path.  Off by default; on the pipeline's critical
-// path the flag selects a template instance, so the default kernels are the code they were.
-// Float expressions follow tracker_oracle.c literally and the file is built with
+// Seam wrap mode (the x_wrap flag of GfArgs): detection through the map path, on the horizontally periodic
+// continuation of the frame -- no side margins, the min-distance test on the cylinder.
+// Float expressions follow tracker_oracle.c literally and every tracker unit is built with
 // -ffp-contract=off, so results are bitwise those of the oracle.
-#include <float.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
-#include <cstring>
 #include <mutex>
 #include <hipcub/hipcub.hpp>
 
 #include "tracker_types.h"
+#include "trk_dev.h"
 
 namespace vio360 {
-
-// LDS writes of this wave visible to its own later reads (no workgroup barrier)
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Tile of linear block b of an n-block grid such that each XCD works on one contiguous range of tiles:
-// blocks b and b + 8 share an XCD (round-robin dispatch, MI355X_MICROARCH.md "Workgroup dispatch"), so
-// neighbouring tiles read their shared halo lines through one L2 instead of fetching them once per XCD
-// (speed only: any placement gives the same results)
-__device__ __forceinline__ int xcd_tile(int b, int n) {
-    const int x = b & 7, s = b >> 3, q = n >> 3, r = n & 7;
-    return x < r ? x * (q + 1) + s : r * (q + 1) + (x - r) * q + s;
-}
-
-__device__ __forceinline__ int reflect101(int p, int n) {
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
-    return p;
-}
-
-// Seam wrap mode: column p of the frame continued periodically, for p in [-n, 2n) -- one conditional add or
-// subtract, no division.  Columns further right are never part of a result (they lie beyond the last output
-// of a partial tile); the min only keeps their address inside the row.
-__device__ __forceinline__ int wrap_x(int p, int n) {
-    return p < 0 ? p + n : (p >= n ? min(p - n, n - 1) : p);
-}
-// the column border of an edge path: REFLECT_101, or the periodic continuation in wrap mode (wave-uniform flag)
-__device__ __forceinline__ int border_x(int p, int n, int x_wrap) { return x_wrap ? wrap_x(p, n) : reflect101(p, n); }
-
-// MASKED: G.static_bits (a region mask's exclusion plane) is part of the static region (pass 1 with a mask set; the
-// maskless instance is the code it was before masks existed)
-template <bool MASKED = false>
-__device__ __forceinline__ bool lm_static_in(const GfArgs& G, int x, int y) {
-    const bool in = y >= G.top_rows && y < G.bottom_start && x >= G.margin && x < G.W - G.margin;
-    if constexpr (MASKED) return in && !((G.static_bits[(size_t)y * G.disc_words + (x >> 5)] >> (x & 31)) & 1u);
-    else return in;
-}
-__device__ __forceinline__ bool lm_disc(const GfArgs& G, int x, int y) {
-    return G.disc_bits && ((G.disc_bits[(size_t)y * G.disc_words + (x >> 5)] >> (x & 31)) & 1u);
-}
-
-// ------------------------------------------------------------------------------------------
-// pyrDown.  Block = 64 x BY outputs; LDS tile of the (2*BY+4) REFLECT_101 source rows, columns
-// [2 ox - 16, 2 ox + 144), staged with 16-B loads (all of a thread's loads issued before its LDS stores; the
-// few reflected columns at the left / right image edge are patched bytewise); each thread makes two adjacent
-// outputs in BY / 8 rows.  BY = 8 (BY = 32 for the large levels -- a quarter of the blocks and of the halo
-// rows, the 3840 x 1920 level-1 launch in one round of resident workgroups -- measured 15.0 against 13.2 us,
-// profiles/r6c_ab_pyr.log).
-constexpr int PD_BX = 64;
-constexpr int PD_TW = 160;
-// WRAP (seam wrap mode, src.x_wrap): the edge columns are patched from the opposite side of the level instead of
-// reflected; the default instance is the code as it was
-template <int BY, bool WRAP = false>
-__global__ void __launch_bounds__(256) pyr_down_kernel(PyrLevelPair src, PyrLevelPair dst) {
-    constexpr int PD_BY = BY, PD_TH = 2 * PD_BY + 4;
-    __shared__ uint8_t tile[PD_TH][PD_TW];
-    const int gxy = gridDim.x * gridDim.y;
-    const int t = xcd_tile(blockIdx.x + gridDim.x * blockIdx.y + gxy * blockIdx.z, gxy * gridDim.z);
-    const int f = t / gxy, bxy = t - f * gxy, bx = bxy % gridDim.x, by = bxy / gridDim.x;
-    const uint8_t* s = f == 0 ? src.p0 : src.p1;
-    uint8_t* d = f == 0 ? dst.p0 : dst.p1;
-    const int sw = src.w, sh = src.h, sp = src.pitch;
-    const int dw = dst.w, dh = dst.h, dp = dst.pitch;
-    const int ox = bx * PD_BX, oy = by * PD_BY;
-    const int cx0 = 2 * ox - 16, sy0 = 2 * oy - 2;  // tile column 0 = source x cx0
-    {  // 16-B chunks of the REFLECT_101 rows; chunks beyond the pitch are skipped
-        constexpr int NCH = PD_TH * (PD_TW / 16);
-        uint4 v[(NCH + 255) / 256];
-#pragma unroll
-        for (int it = 0; it < (NCH + 255) / 256; ++it) {
-            const int e = threadIdx.x + 256 * it;
-            const int x0 = cx0 + 16 * (e % (PD_TW / 16));
-            v[it] = make_uint4(0u, 0u, 0u, 0u);
-            if (e < NCH && x0 >= 0 && x0 + 16 <= sp)
-                v[it] = *reinterpret_cast<const uint4*>(s + (size_t)reflect101(sy0 + e / (PD_TW / 16), sh) * sp + x0);
-        }
-#pragma unroll
-        for (int it = 0; it < (NCH + 255) / 256; ++it) {
-            const int e = threadIdx.x + 256 * it;
-            const int x0 = cx0 + 16 * (e % (PD_TW / 16));
-            if (e < NCH && x0 >= 0 && x0 + 16 <= sp)
-                *reinterpret_cast<uint4*>(&tile[e / (PD_TW / 16)][16 * (e % (PD_TW / 16))]) = v[it];
-        }
-    }
-    if (2 * ox - 2 < 0 || 2 * ox + 2 * PD_BX + 2 > sw) {  // left / right image edge: reflected columns
-        __syncthreads();
-        for (int e = threadIdx.x; e < PD_TH * (2 * PD_BX + 4); e += 256) {
-            const int ty = e / (2 * PD_BX + 4), x = 2 * ox - 2 + e % (2 * PD_BX + 4);
-            if (x < 0 || x >= sw)
-                tile[ty][x - cx0] = s[(size_t)reflect101(sy0 + ty, sh) * sp + (WRAP ? wrap_x(x, sw) : reflect101(x, sw))];
-        }
-    }
-    __syncthreads();
-    const int q = threadIdx.x % (PD_BX / 2);  // outputs 2q, 2q+1 of rows ty0 + 8 r
-#pragma unroll
-    for (int rr = 0; rr < PD_BY / 8; ++rr) {
-        const int ty = threadIdx.x / (PD_BX / 2) + 8 * rr;
-        const int y = oy + ty;
-        if (y >= dh) break;
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int tx = 2 * q + j;
-            int tot = 0;
-#pragma unroll
-            for (int ky = 0; ky < 5; ++ky) {
-                const uint8_t* r = &tile[2 * ty + ky][2 * tx + 14];
-                const int rs = r[0] + 4 * r[1] + 6 * r[2] + 4 * r[3] + r[4];
-                tot += (ky == 0 || ky == 4 ? 1 : (ky == 2 ? 6 : 4)) * rs;
-            }
-            packed |= (uint32_t)((tot + 128) >> 8) << (8 * j);
-        }
-        const int x = ox + 2 * q;
-        if (x + 1 < dw && ((dp & 1) == 0)) {
-            *reinterpret_cast<uint16_t*>(d + (size_t)y * dp + x) = (uint16_t)packed;
-        } else {
-            for (int j = 0; j < 2; ++j)
-                if (x + j < dw) d[(size_t)y * dp + x + j] = (uint8_t)(packed >> (8 * j));
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// LK.  One workgroup per point.
-constexpr int LK_WAVES = 4;  // one point per workgroup of LK_WAVES waves
-constexpr int LK_THREADS = 64 * LK_WAVES;
-constexpr int LK_NIT = (LK_WIN_MAX * LK_WIN_MAX + LK_THREADS - 1) / LK_THREADS;  // patch pixels per lane
-// (LK_T, LK_D, LK_MARGIN, LK_R: the staging tiles' sizes, tracker_types.h)
-
-struct LkShared {
-    uint8_t Jr[LK_R * LK_R];                 // next-frame region (reflect-101 values), origin (rx0, ry0)
-    uint8_t It[LK_T * LK_T];
-    int16_t dx[LK_D * LK_D], dy[LK_D * LK_D];
-};
-
-// Wave sum of integer partials, exact while |sum| < 2^53: the partials are summed as doubles
-// (integer-valued, so every order gives the same exact value) with DPP row reductions (xor 1, xor 2,
-// half-row mirror, row mirror: VALU lane moves, no LDS crossbar) and the four row totals read out.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_d(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-#define DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
-
-__device__ __forceinline__ void lk_weights(float a, float b, int& w00, int& w01, int& w10, int& w11) {
-    w00 = (int)rintf((1.f - a) * (1.f - b) * 16384.f);
-    w01 = (int)rintf(a * (1.f - b) * 16384.f);
-    w10 = (int)rintf((1.f - a) * b * 16384.f);
-    w11 = 16384 - w00 - w01 - w10;
-}
-
-// workgroup sum of integer partials (exact: each wave's partials summed as doubles with DPP row
-// reductions and the four row totals read out, then the LK_WAVES wave totals
-// added in wave order through LDS); every thread gets the total.  red: LK_WAVES doubles of LDS.
-__device__ __forceinline__ long long wg_sum_i64(long long v, double* red) {
-    double d = (double)v;
-    d += dpp_d<0xB1>(d);
-    d += dpp_d<0x4E>(d);
-    d += dpp_d<0x141>(d);
-    d += dpp_d<0x140>(d);
-    const double ws = ((lane_d(d, 0) + lane_d(d, 16)) + lane_d(d, 32)) + lane_d(d, 48);
-    const int wid = threadIdx.x >> 6;
-    __syncthreads();  // red is free (the previous sum's readers are done)
-    if ((threadIdx.x & 63) == 0) red[wid] = ws;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < LK_WAVES; ++q) t += red[q];
-    return (long long)t;
-}
-
-// Seam wrap mode: the column of the frame under the unwrapped column x0 of a staged tile's origin.  The iteration
-// may carry x0 any distance from the frame, so this is a true remainder -- once per staged tile, workgroup-uniform,
-// never per pixel.
-__device__ __forceinline__ int lk_fold_origin(int x0, int w) {
-    const int m = x0 % w;
-    return m < 0 ? m + w : m;
-}
-
-// make the staged region cover the (win+1)^2 window at (ix, iy); restage around it when it does
-// not (one global round trip per level instead of one per iteration).  Values are the
-// REFLECT_101-padded pixels, exactly what a per-window load would read.  Workgroup-uniform.
-// WRAP (seam wrap mode): rx0 stays in the iteration's unwrapped coordinates; the columns are those of the
-// periodic continuation (lk_fold_origin, then one conditional subtract per pixel: w >= LK_R).
-template <bool WRAP>
-__device__ __forceinline__ void lk_region(uint8_t* Jr, int& rx0, int& ry0, const uint8_t* J, int w, int h, int pitch,
-                                          int ix, int iy, int win) {
-    const int D = win + 1;
-    if (ix >= rx0 && iy >= ry0 && ix + D <= rx0 + LK_R && iy + D <= ry0 + LK_R) return;
-    rx0 = ix - LK_MARGIN;
-    ry0 = iy - LK_MARGIN;
-    __syncthreads();  // the previous region's readers are done
-    // every global load of the region is issued before the first LDS store
-    constexpr int NR = (LK_R * LK_R + LK_THREADS - 1) / LK_THREADS;
-    uint32_t v[NR];
-    const int fx0 = WRAP ? lk_fold_origin(rx0, w) : 0;
-#pragma unroll
-    for (int it = 0; it < NR; ++it) {
-        const int e = threadIdx.x + LK_THREADS * it;
-        const int ty = e / LK_R, tx = e - ty * LK_R;
-        v[it] = e < LK_R * LK_R ? J[(size_t)reflect101(ry0 + ty, h) * pitch +
-                                    (WRAP ? wrap_x(fx0 + tx, w) : reflect101(rx0 + tx, w))] : 0u;
-    }
-#pragma unroll
-    for (int it = 0; it < NR; ++it) {
-        const int e = threadIdx.x + LK_THREADS * it;
-        if (e < LK_R * LK_R) Jr[e] = (uint8_t)v[it];
-    }
-    __syncthreads();
-}
-
-// calcOpticalFlowPyrLK for one point per workgroup (LK_WAVES waves): the patch pixels are spread over
-// all lanes (<= LK_NIT each), the window sums are exact integer workgroup sums, so every order gives
-// the sequential values; the per-iteration update is computed by every thread from the same totals.
-template <int NT>
-__device__ void ransac_raw_body(uint32_t seed, uint32_t* raw, uint32_t* mt);  // (RANSAC section)
-__device__ float ransac_cos_bound(float thr);
-__device__ void pixel_to_bearing(float u, float v, int W, int H, float* b);
-constexpr int LK_AUX_BLOCKS = 17;  // LkAux: one workgroup for the raw draws, 16 for the reset and the bitmap clear
-// per-run reset of the GFTT scalars (one thread of gftt_reset_kernel, or of lk_aux in the pipeline)
-__device__ __forceinline__ void gftt_reset_scalars(int* scal) {
-    scal[TS_MAX_ORD] = scal[TS_N_CAND] = scal[TS_N_OUT] = 0;
-    scal[TS_N_TOP] = scal[TS_CUT] = scal[TS_CUT + 1] = scal[TS_INCOMPLETE] = 0;
-    scal[TS_LMAX_OVER] = scal[TS_N_FLAT] = 0;
-}
-__device__ void lk_aux(const LkAux& X, int b) {
-    if (b == 0) {
-        __shared__ uint32_t mt[624];
-        if (X.raw) ransac_raw_body<LK_THREADS>(X.seed, X.raw, mt);
-        if (X.cmin && threadIdx.x == 0) *X.cmin = ransac_cos_bound(X.thresh);
-        return;
-    }
-    const size_t t = (size_t)(b - 1) * LK_THREADS + threadIdx.x, stride = (size_t)(LK_AUX_BLOCKS - 1) * LK_THREADS;
-    if (X.hist) {  // gftt_reset_kernel's work
-        if (t == 0) gftt_reset_scalars(X.scal);
-        for (size_t i = t; i < (size_t)GF_BUCKETS; i += stride) X.hist[i] = 0u;
-        for (size_t i = t; i < X.topk_cap; i += stride) X.topk[i] = 0ull;
-    }
-    if (X.bear0)
-        for (size_t i = t; i < (size_t)X.n; i += stride)
-            pixel_to_bearing(X.pts[2 * i], X.pts[2 * i + 1], X.W, X.H, X.bear0 + 3 * i);
-    if (X.disc) {
-        const size_t n4 = X.disc_words / 4;
-        uint4* d4p = reinterpret_cast<uint4*>(X.disc);
-        if (X.disc_src) {  // a region mask is set: the discs are stamped onto its exclusion plane
-            const uint4* s4p = reinterpret_cast<const uint4*>(X.disc_src);
-            for (size_t i = t; i < n4; i += stride) d4p[i] = s4p[i];
-            for (size_t i = 4 * n4 + t; i < X.disc_words; i += stride) X.disc[i] = X.disc_src[i];
-        } else {
-            for (size_t i = t; i < n4; i += stride) d4p[i] = make_uint4(0u, 0u, 0u, 0u);
-            for (size_t i = 4 * n4 + t; i < X.disc_words; i += stride) X.disc[i] = 0u;
-        }
-    }
-}
-
-// Guided search: the start position (gx, gy) of point pt at the top level, in level-0 pixels; on entry the point's
-// previous position (px, py), which stays when the point has no usable guess.  Workgroup-uniform.
-//   LK_GUESS_PTS  A.guess[pt]
-//   LK_GUESS_ROT  Camera::BearingToPixel(R * PixelToBearing(prev)) (Camera.cpp:22-67) in f32, operations in this
-//                 order: r_i = ((R_i0 b0 + R_i1 b1) + R_i2 b2), theta = atan2f(r0, r2), phi = -asinf(r1 / |r|),
-//                 u = W (0.5 + theta / 2pi), v = H (0.5 - phi / pi)
-// A guess that is not finite or lies outside [-W, 2W) x [-H, 2H) counts as absent (OpenCV would index with it).
-// WRAP: x folded into [0, W) by one f32 +-W, as the final fold of the tracked column.
-template <bool WRAP>
-__device__ __forceinline__ void lk_guess(const LkArgs& A, int pt, float px, float py, float& gx, float& gy) {
-    const int W = A.lv[0].w, H = A.lv[0].h;
-    const float Wf = (float)W, Hf = (float)H;
-    float u, v;
-    if (A.guided == LK_GUESS_ROT) {
-        float b[3];
-        pixel_to_bearing(px, py, W, H, b);
-        const float r0 = (A.rot[0] * b[0] + A.rot[1] * b[1]) + A.rot[2] * b[2];
-        const float r1 = (A.rot[3] * b[0] + A.rot[4] * b[1]) + A.rot[5] * b[2];
-        const float r2 = (A.rot[6] * b[0] + A.rot[7] * b[1]) + A.rot[8] * b[2];
-        const float nr = sqrtf((r0 * r0 + r1 * r1) + r2 * r2);
-        const float theta = atan2f(r0, r2);
-        const float phi = -asinf(fminf(fmaxf(r1 / nr, -1.f), 1.f));
-        u = Wf * (0.5f + theta / 6.2831855f);
-        v = Hf * (0.5f - phi / 3.1415927f);
-    } else {
-        u = A.guess[2 * pt];
-        v = A.guess[2 * pt + 1];
-    }
-    if (!(u >= -Wf && u < 2.f * Wf && v >= -Hf && v < 2.f * Hf)) return;  // (a NaN fails every comparison)
-    if (WRAP) {
-        if (u < 0.f) u += Wf;
-        else if (u >= Wf) u -= Wf;
-        if (u == Wf) u = 0.f;  // (a tiny negative column rounds up to W)
-    }
-    gx = u;
-    gy = v;
-}
-
-// WRAP (seam wrap mode, A.x_wrap): every level is the periodic continuation of the frame in x -- tile columns
-// modulo the level width, no "left the frame" test in x, the iteration in unwrapped coordinates; only the final
-// next.x is folded into [0, W) by one f32 +-W.  The default instance is the code it was before the mode existed.
-// GUIDED (OPTFLOW_USE_INITIAL_FLOW, A.guided): the top level starts at the point's guess (lk_guess) instead of its
-// previous position; nothing else differs, and a guess equal to the previous position gives the unguided bits.  The
-// two unguided instances are the code they were before the guided ones existed.
-// FB (round-trip check, A.fb): after the forward search and its fold the workgroup of a found point runs the level
-// loop once more with the frames' roles swapped -- the point its own next, the top level started at the previous
-// position (always "guided") -- then tests where it lands against the previous position.  next, err, guess_out and
-// bear1 are the forward search's; status is stored once, as forward AND pass.  The LDS tiles and red are reused;
-// every branch on status is workgroup-uniform.  The four instances without FB are the code they were.
-// The rules a guess passes, for the backward direction of the round-trip check (lk_guess applies the same to its
-// own): (u, v) replaces (gx, gy) unless it is not finite or lies outside [-W, 2W) x [-H, 2H); WRAP folds x into [0, W).
-template <bool WRAP>
-__device__ __forceinline__ void lk_guess_at(float Wf, float Hf, float u, float v, float& gx, float& gy) {
-    if (!(u >= -Wf && u < 2.f * Wf && v >= -Hf && v < 2.f * Hf)) return;  // (a NaN fails every comparison)
-    if (WRAP) {
-        if (u < 0.f) u += Wf;
-        else if (u >= Wf) u -= Wf;
-        if (u == Wf) u = 0.f;  // (a tiny negative column rounds up to W)
-    }
-    gx = u;
-    gy = v;
-}
-
-template <bool WRAP, bool GUIDED = false, bool FB = false>
-__global__ void __launch_bounds__(LK_THREADS) lk_kernel(LkArgs A, LkAux X) {
-    __shared__ LkShared S;
-    __shared__ double red[LK_WAVES];
-    const int tid = threadIdx.x;
-    const int pt = blockIdx.x;
-    if (pt >= A.n) {  // whole workgroup
-        lk_aux(X, pt - A.n);
-        return;
-    }
-    const int win = A.win;
-    const float hw = (win - 1) * 0.5f;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    const int np = win * win;
-    float prev_x = A.pts[2 * pt], prev_y = A.pts[2 * pt + 1];
-    float nxt_x = 0.f, nxt_y = 0.f;
-    int status = 1;
-    float err = 0.f;
-    float gs_x = prev_x, gs_y = prev_y;  // GUIDED: the top level's start position in level-0 pixels
-    if constexpr (GUIDED) {
-        lk_guess<WRAP>(A, pt, prev_x, prev_y, gs_x, gs_y);
-        if (A.guess_out && tid == 128) {
-            A.guess_out[2 * pt] = gs_x;
-            A.guess_out[2 * pt + 1] = gs_y;
-        }
-    }
-    // FB: the forward result while the backward direction runs, and the check's outputs.  The second direction is
-    // a jump back to `direction`, not a loop around the level loop: without FB the label is no branch target, and
-    // the compiler emits the instructions it emitted before the check existed.
-    float fw_x = 0.f, fw_y = 0.f, fw_err = 0.f, bk_x = 0.f, bk_y = 0.f, fb_d2 = 0.f;
-    int fb_state = LK_FB_NOT_RUN, dir = 0;
-direction:
-    for (int level = A.levels; level >= 0; --level) {
-        const LkLevel& Lv = A.lv[level];
-        const int w = Lv.w, h = Lv.h;
-        const uint8_t* I = FB && dir ? Lv.curr : Lv.prev;  // (the backward direction: the frames swap roles)
-        const uint8_t* J = FB && dir ? Lv.prev : Lv.curr;
-        const float sc = (float)(1. / (1 << level));
-        float px = prev_x * sc, py = prev_y * sc;
-        float nx, ny;
-        if (level == A.levels) {
-            if constexpr (GUIDED || FB) { nx = gs_x * sc; ny = gs_y * sc; }
-            else { nx = px; ny = py; }
-        } else { nx = nxt_x * 2.f; ny = nxt_y * 2.f; }
-        nxt_x = nx; nxt_y = ny;
-        px -= hw; py -= hw;
-        const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-        if ((!WRAP && (ipx < -win || ipx >= w)) || ipy < -win || ipy >= h) {
-            if (level == 0) { status = 0; err = 0.f; }
-            continue;
-        }
-        // stage the prev tile: rows ipy-1 .. ipy+win+1, cols ipx-1 .. ipx+win+1
-        const int T = win + 3;
-        __syncthreads();  // the previous level's readers of It / dx / dy are done
-        {
-            constexpr int NT = (LK_T * LK_T + LK_THREADS - 1) / LK_THREADS;  // loads first, then the LDS stores
-            uint32_t v[NT];
-            const int fx0 = WRAP ? lk_fold_origin(ipx - 1, w) : 0;
-#pragma unroll
-            for (int it = 0; it < NT; ++it) {
-                const int e = tid + LK_THREADS * it;
-                const int ty = e / T, tx = e - (e / T) * T;
-                v[it] = e < T * T ? I[(size_t)reflect101(ipy - 1 + ty, h) * Lv.pitch +
-                                      (WRAP ? wrap_x(fx0 + tx, w) : reflect101(ipx - 1 + tx, w))] : 0u;
-            }
-#pragma unroll
-            for (int it = 0; it < NT; ++it) {
-                const int e = tid + LK_THREADS * it;
-                if (e < T * T) S.It[e] = (uint8_t)v[it];
-            }
-        }
-        __syncthreads();
-        // Scharr derivatives at (ipx+tx, ipy+ty), tx,ty in [0, win]; zero outside the image
-        const int D = win + 1;
-        for (int e = tid; e < D * D; e += LK_THREADS) {
-            int ty = e / D, tx = e % D;
-            int X = ipx + tx, Y = ipy + ty;
-            int gx = 0, gy = 0;
-            if ((WRAP || X >= 0) && Y >= 0 && (WRAP || X < w) && Y < h) {
-                const uint8_t* r0 = &S.It[ty * T + tx];      // (X-1, Y-1)
-                const uint8_t* r1 = r0 + T;
-                const uint8_t* r2 = r1 + T;
-                int t0m = (r0[0] + r2[0]) * 3 + r1[0] * 10, t0p = (r0[2] + r2[2]) * 3 + r1[2] * 10;
-                int t1m = r2[0] - r0[0], t1c = r2[1] - r0[1], t1p = r2[2] - r0[2];
-                gx = (int16_t)(t0p - t0m);
-                gy = (int16_t)((t1p + t1m) * 3 + t1c * 10);
-            }
-            S.dx[e] = (int16_t)gx;
-            S.dy[e] = (int16_t)gy;
-        }
-        __syncthreads();
-        float a = px - ipx, b = py - ipy;
-        int w00, w01, w10, w11;
-        lk_weights(a, b, w00, w01, w10, w11);
-        // the lane's patch pixels e = tid + LK_THREADS it: interpolated I and derivatives stay in registers
-        // for all iterations of the level; joff = offset of the pixel in the next-frame window (-1: none)
-        int joff[LK_NIT], iwv[LK_NIT], ixr[LK_NIT], iyr[LK_NIT];
-        int sA11 = 0, sA12 = 0, sA22 = 0;
-#pragma unroll
-        for (int it = 0; it < LK_NIT; ++it) {
-            const int e = tid + LK_THREADS * it;
-            joff[it] = -1;
-            iwv[it] = ixr[it] = iyr[it] = 0;
-            if (e < np) {
-                const int y = e / win, x = e - (e / win) * win;
-                const uint8_t* t = &S.It[(y + 1) * T + x + 1];
-                const int ival = DESCALE(t[0] * w00 + t[1] * w01 + t[T] * w10 + t[T + 1] * w11, 9);
-                const int q = y * D + x;
-                const int ixv =
-                    DESCALE(S.dx[q] * w00 + S.dx[q + 1] * w01 + S.dx[q + D] * w10 + S.dx[q + D + 1] * w11, 14);
-                const int iyv =
-                    DESCALE(S.dy[q] * w00 + S.dy[q + 1] * w01 + S.dy[q + D] * w10 + S.dy[q + D + 1] * w11, 14);
-                iwv[it] = (int16_t)ival;
-                ixr[it] = (int16_t)ixv;
-                iyr[it] = (int16_t)iyv;
-                joff[it] = y * LK_R + x;
-                sA11 += ixv * ixv;
-                sA12 += ixv * iyv;
-                sA22 += iyv * iyv;
-            }
-        }
-        const long long tA11 = wg_sum_i64(sA11, red), tA12 = wg_sum_i64(sA12, red), tA22 = wg_sum_i64(sA22, red);
-        const float A11 = (float)tA11 * FLT_SCALE, A12 = (float)tA12 * FLT_SCALE, A22 = (float)tA22 * FLT_SCALE;
-        float Dt = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win * win);
-        if (minEig < A.min_eig || Dt < FLT_EPSILON) {
-            if (level == 0) status = 0;
-            continue;
-        }
-        Dt = 1.f / Dt;
-        nx -= hw; ny -= hw;
-        float pdx = 0.f, pdy = 0.f;
-        int rx0 = -(1 << 29), ry0 = -(1 << 29);  // no region staged for this level yet
-        for (int j = 0; j < A.max_iters; ++j) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if ((!WRAP && (inx < -win || inx >= w)) || iny < -win || iny >= h) {
-                if (level == 0) status = 0;
-                break;
-            }
-            a = nx - inx; b = ny - iny;
-            lk_weights(a, b, w00, w01, w10, w11);
-            lk_region<WRAP>(S.Jr, rx0, ry0, J, w, h, Lv.pitch, inx, iny, win);
-            const uint8_t* Jw = S.Jr + (iny - ry0) * LK_R + (inx - rx0);
-            int ib1 = 0, ib2 = 0;
-#pragma unroll
-            for (int it = 0; it < LK_NIT; ++it) {
-                if (joff[it] >= 0) {
-                    const uint8_t* t = Jw + joff[it];
-                    const int diff = DESCALE(t[0] * w00 + t[1] * w01 + t[LK_R] * w10 + t[LK_R + 1] * w11, 9) - iwv[it];
-                    ib1 += diff * ixr[it];
-                    ib2 += diff * iyr[it];
-                }
-            }
-            const float b1 = (float)wg_sum_i64(ib1, red) * FLT_SCALE, b2 = (float)wg_sum_i64(ib2, red) * FLT_SCALE;
-            const float ddx = (A12 * b2 - A22 * b1) * Dt;
-            const float ddy = (A12 * b1 - A11 * b2) * Dt;
-            nx += ddx; ny += ddy;
-            nxt_x = nx + hw; nxt_y = ny + hw;
-            if ((double)ddx * ddx + (double)ddy * ddy <= A.eps2) break;
-            if (j > 0 && fabs((double)(ddx + pdx)) < 0.01 && fabs((double)(ddy + pdy)) < 0.01) {
-                nxt_x -= ddx * 0.5f;
-                nxt_y -= ddy * 0.5f;
-                break;
-            }
-            pdx = ddx; pdy = ddy;
-        }
-        if (status && level == 0) {
-            const float fx = nxt_x - hw, fy = nxt_y - hw;
-            const int ix = (int)floorf(fx), iy = (int)floorf(fy);
-            if ((!WRAP && (ix < -win || ix >= w)) || iy < -win || iy >= h) {
-                status = 0;
-            } else {
-                lk_weights(fx - ix, fy - iy, w00, w01, w10, w11);
-                lk_region<WRAP>(S.Jr, rx0, ry0, J, w, h, Lv.pitch, ix, iy, win);
-                const uint8_t* Jw = S.Jr + (iy - ry0) * LK_R + (ix - rx0);
-                long long es = 0;
-#pragma unroll
-                for (int it = 0; it < LK_NIT; ++it) {
-                    if (joff[it] >= 0) {
-                        const uint8_t* t = Jw + joff[it];
-                        const int diff =
-                            DESCALE(t[0] * w00 + t[1] * w01 + t[LK_R] * w10 + t[LK_R + 1] * w11, 9) - iwv[it];
-                        es += diff < 0 ? -diff : diff;
-                    }
-                }
-                es = wg_sum_i64(es, red);
-                err = (float)es * (1.f / (32 * win * win));
-            }
-        }
-    }
-    if (WRAP) {  // fold the tracked column into [0, W): one +-W (exact for a point within one turn of the frame)
-        const float Wf = (float)A.lv[0].w;
-        if (nxt_x < 0.f) nxt_x += Wf;
-        else if (nxt_x >= Wf) nxt_x -= Wf;
-        if (nxt_x == Wf) nxt_x = 0.f;  // (a tiny negative column rounds up to W)
-        if (!(nxt_x >= 0.f && nxt_x < Wf)) {  // more than a turn away, or not a number: the point is lost
-            nxt_x = 0.f;
-            status = 0;
-            err = 0.f;
-        }
-    }
-    if constexpr (FB) {
-        const float Wf = (float)A.lv[0].w, Hf = (float)A.lv[0].h;
-        if (dir == 0) {
-            fw_x = nxt_x; fw_y = nxt_y; fw_err = err;
-            if (status) {  // found (workgroup-uniform): track it back
-                // the point is its own next, the guess its previous position under lk_guess's rules.  The level
-                // loop's first LDS access follows a barrier, so the tiles and red are free as at a level change.
-                prev_x = gs_x = nxt_x;
-                prev_y = gs_y = nxt_y;
-                lk_guess_at<WRAP>(Wf, Hf, A.pts[2 * pt], A.pts[2 * pt + 1], gs_x, gs_y);
-                err = 0.f;
-                dir = 1;
-                goto direction;
-            }
-        } else {
-            bk_x = nxt_x; bk_y = nxt_y;
-            float dx = bk_x - A.pts[2 * pt];
-            const float dy = bk_y - A.pts[2 * pt + 1];
-            if (WRAP) {  // the short way round
-                const float half = Wf * 0.5f;
-                if (dx > half) dx -= Wf;
-                else if (dx < -half) dx += Wf;
-            }
-            const float d2 = dx * dx + dy * dy;
-            const bool pass = status && d2 <= A.fb_max_dist * A.fb_max_dist;  // (a NaN fails)
-            fb_state = !status ? LK_FB_BACK_LOST : pass ? LK_FB_PASS : LK_FB_TOO_FAR;
-            fb_d2 = status ? d2 : 0.f;
-            nxt_x = fw_x; nxt_y = fw_y; err = fw_err;
-            status = pass;
-        }
-    }
-    if (tid == 0) {
-        A.next[2 * pt] = nxt_x;
-        A.next[2 * pt + 1] = nxt_y;
-        A.status[pt] = (uint8_t)status;
-        A.err[pt] = err;
-    }
-    // the tracked point's bearing (RANSAC's input, FeatureTracker.cpp:262-271) by another wave, beside the stores
-    if (A.bear1 && tid == 64) pixel_to_bearing(nxt_x, nxt_y, A.lv[0].w, A.lv[0].h, A.bear1 + 3 * pt);
-    if constexpr (FB) {
-        if (tid == 192) {
-            A.back[2 * pt] = bk_x;
-            A.back[2 * pt + 1] = bk_y;
-            A.fb_state[pt] = (uint8_t)fb_state;
-            A.fb_d2[pt] = fb_d2;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// bearings / filter / RANSAC
-__device__ void pixel_to_bearing(float u, float v, int W, int H, float* b) {
-    float un = u / (float)W, vn = v / (float)H;
-    float lon = (float)((double)((un - 0.5f) * 2.0f) * M_PI);
-    float lat = (float)((double)(-(vn - 0.5f)) * M_PI);
-    float cl = (float)cos((double)lat), sl = (float)sin((double)lat);
-    float so = (float)sin((double)lon), co = (float)cos((double)lon);
-    float x = cl * so, y = -sl, z = cl * co;
-    float sq = (x * x + y * y) + z * z;
-    if (sq > 0.f) {
-        float nr = sqrtf(sq);
-        x /= nr; y /= nr; z /= nr;
-    }
-    b[0] = x; b[1] = y; b[2] = z;
-}
-
-// order-preserving compaction of the RANSAC input (single workgroup of RP_THREADS: four waves get a CU
-// sooner than sixteen while GFTT pass 1 occupies the chip from the side stream):
-//   mode 0: all n points (erp_rot_ransac); mode 1: status ∧ !polar ∧ !boundary (pipeline)
-constexpr int RP_THREADS = 256;
-// WRAP: seam wrap mode (R.x_wrap); the default instance is the code as it was
-template <int NT, bool WRAP = false>
-__device__ int ransac_prep_body(const RansacArgs& R, int* wsum, int& base) {
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    const int n = R.n;
-    for (int c0 = 0; c0 < n; c0 += NT) {
-        int i = c0 + threadIdx.x;
-        int good = 0;
-        if (i < n) {
-            if (R.mode == 0) good = 1;
-            else {
-                float x = R.p1[2 * i], y = R.p1[2 * i + 1];
-                float vr = y / (float)R.H;
-                bool polar = (vr < R.polar_ratio) || (vr > (1.0f - R.polar_ratio));
-                float m = (float)R.margin;
-                // (seam wrap mode: no left / right margin, x is already folded into [0, W))
-                bool nearb = WRAP ? (y < m) || (y > (float)R.H - m)
-                                  : (x < m) || (x > (float)R.W - m) || (y < m) || (y > (float)R.H - m);
-                good = R.status[i] && !polar && !nearb;
-                if (R.excl_bits && good) {  // region mask: the pixel the point rounds to (as the disc centres)
-                    int xi = (int)rintf(x);
-                    const int yi = (int)rintf(y);
-                    if (WRAP && xi == R.W) xi = 0;  // a column within half a pixel of the seam rounds across it
-                    good = (unsigned)xi < (unsigned)R.W && (unsigned)yi < (unsigned)R.H &&
-                           !((R.excl_bits[(size_t)yi * R.excl_words + (xi >> 5)] >> (xi & 31)) & 1u);
-                }
-            }
-            R.kept[i] = 0;
-        }
-        unsigned long long bal = __ballot(good);
-        int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        int pre = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int k = 0; k < wid; ++k) off += wsum[k];
-        if (good) {
-            int j = off + pre;
-            R.gidx[j] = i;
-            if (R.bear0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    R.b0[3 * j + c] = R.bear0[3 * i + c];
-                    R.b1[3 * j + c] = R.bear1[3 * i + c];
-                }
-            } else {
-                pixel_to_bearing(R.p0[2 * i], R.p0[2 * i + 1], R.W, R.H, R.b0 + 3 * j);
-                pixel_to_bearing(R.p1[2 * i], R.p1[2 * i + 1], R.W, R.H, R.b1 + 3 * j);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int t = 0;
-            for (int k = 0; k < NT / 64; ++k) t += wsum[k];
-            base += t;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *R.n_good = base;
-    return base;
-}
-// The inlier test (float)acos((double)c) < thr (FeatureTracker.cpp:365-375 + Camera::AngularDistance, Camera.cpp:89-98,
-// in the oracle's form) is
-// monotone non-increasing in the float cosine c, so it is c >= c_min for the smallest float c in [-1, 1] that
-// passes it: found once per run by bisection over the floats' order (31 evaluations of the same acos), every
-// hypothesis' inlier count is then a compare per point instead of a double acos.  (Adjacent floats near the
-// crossing differ in acos by ~1e-6, far above the double evaluation's error: the two tests agree bit for bit.)
-// +inf when no cosine passes (an empty inlier set: no c >= +inf; NaN compares false in both forms).
-__device__ float ransac_cos_bound(float thr) {
-    auto pass = [&](float c) { return (float)acos((double)c) < thr; };
-    auto ord = [](float x) {
-        const uint32_t b = __float_as_uint(x);
-        return (b >> 31) ? ~b : (b | 0x80000000u);
-    };
-    auto unord = [](uint32_t m) { return __uint_as_float((m >> 31) ? (m & 0x7fffffffu) : ~m); };
-    if (!pass(1.0f)) return INFINITY;
-    uint32_t lo = ord(-1.0f), hi = ord(1.0f);  // pass(unord(hi)) holds throughout
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (pass(unord(mid))) hi = mid;
-        else lo = mid + 1;
-    }
-    return unord(hi);
-}
-
-__global__ void __launch_bounds__(RP_THREADS) ransac_prep_kernel(RansacArgs R) {
-    __shared__ int wsum[RP_THREADS / 64];
-    __shared__ int base;
-    ransac_prep_body<RP_THREADS>(R, wsum, base);
-    if (threadIdx.x == 0) *R.cmin = ransac_cos_bound(R.thresh);
-}
-
-// mt19937 + libstdc++-11 uniform_int_distribution (Lemire) — the reference's sampler
-// (FeatureTracker.cpp:273-288) with an injected seed; one thread (the stream is sequential).
-struct Mt19937 {
-    uint32_t mt[624];
-    int idx;
-    __device__ void seed(uint32_t s) {
-        mt[0] = s;
-        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-        idx = 624;
-    }
-    __device__ uint32_t next() {
-        if (idx >= 624) {
-            for (int i = 0; i < 624; ++i) {
-                uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);
-                mt[i] = mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-            }
-            idx = 0;
-        }
-        uint32_t y = mt[idx++];
-        y ^= y >> 11;
-        y ^= (y << 7) & 0x9d2c5680u;
-        y ^= (y << 15) & 0xefc60000u;
-        y ^= y >> 18;
-        return y;
-    }
-};
-__device__ uint32_t uniform_below(Mt19937& g, uint32_t range) {  // uniform in [0, range)
-    uint64_t prod = (uint64_t)g.next() * range;
-    uint32_t low = (uint32_t)prod;
-    if (low < range) {
-        uint32_t thr = (uint32_t)(-range) % range;
-        while (low < thr) {
-            prod = (uint64_t)g.next() * range;
-            low = (uint32_t)prod;
-        }
-    }
-    return (uint32_t)(prod >> 32);
-}
-
-// Parallel form of the same stream (one workgroup): the raw mt19937 words of RS_BLOCKS state
-// blocks are generated by a three-phase parallel twist (i in [0,227) reads only old words;
-// [227,454) and [454,624) read words that the previous phase produced) and tempered in parallel;
-// uniform_int_distribution's rejection test depends on a word alone, so accepted draws are a
-// prefix-scan compaction; a hypothesis consumes draws until it holds 3 distinct indices, and the
-// hypothesis chain is followed one wave at a time, 64 hypotheses per step while each consumes
-// exactly 3 draws (the common case).  Bitwise the sequential sampler; if the generated stream runs
-// out (tiny n: many duplicate redraws) the sequential sampler runs instead.
-constexpr int RS_THREADS = 1024;
-constexpr int RS_BLOCKS = 8;
-constexpr int RS_RAW = 624 * RS_BLOCKS;
-__device__ void ransac_sample_seq(const RansacArgs& R, Mt19937& g, int n) {
-    g.seed(R.seed);
-    for (int it = 0; it < R.iters; ++it) {
-        int got[3];
-        int k = 0;
-        while (k < 3) {
-            int idx = (int)uniform_below(g, (uint32_t)n);
-            bool dup = false;
-            for (int q = 0; q < k; ++q) dup |= got[q] == idx;
-            if (!dup) got[k++] = idx;
-        }
-        R.samples[3 * it] = got[0];
-        R.samples[3 * it + 1] = got[1];
-        R.samples[3 * it + 2] = got[2];
-    }
-}
-// the first RS_RAW tempered outputs of mt19937(seed): seeding recurrence, RS_BLOCKS twists of the
-// 624-word state (three dependency-free phases each) and tempering.  Depends on the seed only, so
-// the tracker pipeline runs it on its side stream while the frames are processed.
-template <int NT>
-__device__ void ransac_raw_body(uint32_t seed, uint32_t* raw, uint32_t* mt) {
-    static_assert(NT >= 227, "one twist element per thread and phase");
-    const int tid = threadIdx.x;
-    if (tid == 0) {  // seeding recurrence (sequential, 623 steps)
-        uint32_t v = seed;
-        mt[0] = v;
-        for (int i = 1; i < 624; ++i) {
-            v = 1812433253u * (v ^ (v >> 30)) + (uint32_t)i;
-            mt[i] = v;
-        }
-    }
-    __syncthreads();
-    for (int blk = 0; blk < RS_BLOCKS; ++blk) {
-        // twist: phases [0,227) [227,454) [454,624)
-        const int lo[3] = {0, 227, 454}, hi[3] = {227, 454, 624};
-        for (int ph = 0; ph < 3; ++ph) {
-            const int i = lo[ph] + tid;
-            uint32_t nv = 0;
-            if (i < hi[ph]) {
-                const uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);
-                nv = mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-            }
-            __syncthreads();
-            if (i < hi[ph]) mt[i] = nv;
-            __syncthreads();
-        }
-        for (int i = tid; i < 624; i += NT) {
-            uint32_t y = mt[i];
-            y ^= y >> 11;
-            y ^= (y << 7) & 0x9d2c5680u;
-            y ^= (y << 15) & 0xefc60000u;
-            y ^= y >> 18;
-            raw[624 * blk + i] = y;
-        }
-        __syncthreads();  // the next twist overwrites mt
-    }
-}
-__global__ void __launch_bounds__(RS_THREADS) ransac_raw_kernel(uint32_t seed, uint32_t* raw) {
-    __shared__ uint32_t mt[624];
-    ransac_raw_body<RS_THREADS>(seed, raw, mt);
-}
-
-// PREP: the input compaction (ransac_prep_body) first, in the same workgroup (one launch fewer on the
-// tracker's critical path); the sampler then reads the count from LDS.  Four waves (a sixteen-wave
-// workgroup waits longer for a CU while GFTT pass 1 fills the chip from the side stream): thread t
-// tests the RS_CHUNK contiguous stream words [t RS_CHUNK, (t+1) RS_CHUNK), one block scan of the
-// per-thread accept counts places its accepted draws in stream order.
-constexpr int RS_SAMPLE_THREADS = 256;
-constexpr int RS_CHUNK = 20;
-static_assert(RS_CHUNK % 4 == 0 && RS_RAW % 4 == 0 && RS_SAMPLE_THREADS * RS_CHUNK >= RS_RAW, "sampler chunks");
-template <bool PREP, bool WRAP = false>
-__global__ void __launch_bounds__(RS_SAMPLE_THREADS) ransac_sample_kernel(RansacArgs R) {
-    __shared__ uint32_t acc[RS_RAW];    // accepted draws (compacted), in stream order
-    __shared__ uint8_t len3[RS_RAW];    // 1: a hypothesis starting at draw p consumes exactly 3 draws
-    __shared__ int wsum[RS_SAMPLE_THREADS / 64];
-    __shared__ int s_fallback, s_base;
-#ifdef TRK_STAMPS
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
-    const int n = PREP ? ransac_prep_body<RS_SAMPLE_THREADS, WRAP>(R, wsum, s_base) : *R.n_good;
-#ifdef TRK_STAMPS
-    const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-#endif
-    if (PREP) __syncthreads();  // wsum is reused below
-    if (n < 3 || R.iters <= 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int w0 = tid * RS_CHUNK;
-    uint32_t yw[RS_CHUNK];  // the thread's tempered words (raw: a 256-B aligned allocation)
-#pragma unroll
-    for (int q = 0; q < RS_CHUNK / 4; ++q) {
-        const int w = w0 + 4 * q;
-        const uint4 v = w < RS_RAW ? *reinterpret_cast<const uint4*>(R.raw + w) : make_uint4(0u, 0u, 0u, 0u);
-        yw[4 * q] = v.x;
-        yw[4 * q + 1] = v.y;
-        yw[4 * q + 2] = v.z;
-        yw[4 * q + 3] = v.w;
-    }
-    const uint32_t range = (uint32_t)n;
-    const uint32_t thr = (uint32_t)(-range) % range;
-    auto accepted = [&](int u) {  // uniform_int_distribution's rejection test of word u
-        const uint32_t low = (uint32_t)((uint64_t)yw[u] * range);
-        return w0 + u < RS_RAW && !(low < range && low < thr);
-    };
-    int cnt = 0;
-#pragma unroll
-    for (int u = 0; u < RS_CHUNK; ++u) cnt += accepted(u) ? 1 : 0;
-    int incl = cnt;  // inclusive scan over the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[wid] = incl;
-    __syncthreads();
-    int pos = incl - cnt;
-    for (int q = 0; q < wid; ++q) pos += wsum[q];
-#pragma unroll
-    for (int u = 0; u < RS_CHUNK; ++u)
-        if (accepted(u)) acc[pos++] = (uint32_t)(((uint64_t)yw[u] * range) >> 32);
-    const int M = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    for (int p = tid; p < M; p += RS_SAMPLE_THREADS)
-        len3[p] = (p + 2 < M && acc[p] != acc[p + 1] && acc[p] != acc[p + 2] && acc[p + 1] != acc[p + 2]) ? 1 : 0;
-    __syncthreads();
-#ifdef TRK_STAMPS
-    const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-#endif
-    if (wid == 0) {
-        int s = 0, h = 0;
-        bool fb = false;
-        while (h < R.iters && !fb) {
-            const int p = s + 3 * lane;
-            const bool ok = h + lane < R.iters && p + 2 < M && len3[p];
-            const unsigned long long bad = __ballot(!ok);
-            const int f = bad ? __ffsll((long long)bad) - 1 : 64;
-            if (lane < f) {
-                R.samples[3 * (h + lane)] = (int)acc[p];
-                R.samples[3 * (h + lane) + 1] = (int)acc[p + 1];
-                R.samples[3 * (h + lane) + 2] = (int)acc[p + 2];
-            }
-            s += 3 * f;
-            h += f;
-            if (h >= R.iters) break;
-            if (f < 64) {  // hypothesis h consumes more than 3 draws (a duplicate) or the stream ends
-                int got[3], k = 0, q = s;
-                while (k < 3 && q < M) {
-                    const int idx = (int)acc[q++];
-                    bool dup = false;
-                    for (int u = 0; u < k; ++u) dup |= got[u] == idx;
-                    if (!dup) got[k++] = idx;
-                }
-                if (k < 3) { fb = true; break; }
-                if (lane == 0) {
-                    R.samples[3 * h] = got[0];
-                    R.samples[3 * h + 1] = got[1];
-                    R.samples[3 * h + 2] = got[2];
-                }
-                s = q;
-                ++h;
-            }
-        }
-        if (lane == 0) s_fallback = fb ? 1 : 0;
-    }
-    __syncthreads();
-#ifdef TRK_STAMPS
-    if (tid == 0)
-        printf("ransac_sample: prep %llu draws %llu chain %llu (n %d, M %d)\n", ts1 - ts0, ts2 - ts1,
-               __builtin_amdgcn_s_memtime() - ts2, n, M);
-#endif
-    if (s_fallback && tid == 0) {
-        __shared__ Mt19937 g;  // stream exhausted: the sequential sampler from the seed
-        ransac_sample_seq(R, g, n);
-    }
-}
-
-__device__ void jacobi3(double* A, double* V) {
-    for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double apq = A[3 * p + q];
-                if (apq == 0.0) continue;
-                double app = A[3 * p + p], aqq = A[3 * q + q];
-                double theta = (aqq - app) / (2.0 * apq);
-                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 3; ++k) {
-                    double akp = A[3 * k + p], akq = A[3 * k + q];
-                    A[3 * k + p] = c * akp - s * akq;
-                    A[3 * k + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    double apk = A[3 * p + k], aqk = A[3 * q + k];
-                    A[3 * p + k] = c * apk - s * aqk;
-                    A[3 * q + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    double vkp = V[3 * k + p], vkq = V[3 * k + q];
-                    V[3 * k + p] = c * vkp - s * vkq;
-                    V[3 * k + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
-// EstimateRotation (FeatureTracker.cpp:330-355): nearest proper rotation of H (see oracle)
-__device__ void kabsch_rotation(const float* Hf, float* Rf) {
-    double H[9], HtH[9], V[9];
-    for (int i = 0; i < 9; ++i) H[i] = Hf[i];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) HtH[3 * i + j] = H[i] * H[j] + H[3 + i] * H[3 + j] + H[6 + i] * H[6 + j];
-    jacobi3(HtH, V);
-    double w[3] = {HtH[0], HtH[4], HtH[8]};
-    int idx[3] = {0, 1, 2};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (w[idx[j]] > w[idx[i]]) { int t = idx[i]; idx[i] = idx[j]; idx[j] = t; }
-    double v[3][3], u[3][3];
-    for (int c = 0; c < 3; ++c)
-        for (int r = 0; r < 3; ++r) v[c][r] = V[3 * r + idx[c]];
-    for (int c = 0; c < 2; ++c) {
-        for (int r = 0; r < 3; ++r) u[c][r] = H[3 * r] * v[c][0] + H[3 * r + 1] * v[c][1] + H[3 * r + 2] * v[c][2];
-        double nn = sqrt(u[c][0] * u[c][0] + u[c][1] * u[c][1] + u[c][2] * u[c][2]);
-        if (nn > 0) { u[c][0] /= nn; u[c][1] /= nn; u[c][2] /= nn; }
-    }
-    double d01 = u[0][0] * u[1][0] + u[0][1] * u[1][1] + u[0][2] * u[1][2];
-    for (int r = 0; r < 3; ++r) u[1][r] -= d01 * u[0][r];
-    double n1 = sqrt(u[1][0] * u[1][0] + u[1][1] * u[1][1] + u[1][2] * u[1][2]);
-    if (n1 > 0) { u[1][0] /= n1; u[1][1] /= n1; u[1][2] /= n1; }
-    u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
-    u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
-    u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
-    double dV = v[0][0] * (v[1][1] * v[2][2] - v[1][2] * v[2][1]) - v[1][0] * (v[0][1] * v[2][2] - v[0][2] * v[2][1]) +
-                v[2][0] * (v[0][1] * v[1][2] - v[0][2] * v[1][1]);
-    double d = dV < 0 ? -1.0 : 1.0;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Rf[3 * r + c] = (float)(u[0][r] * v[0][c] + u[1][r] * v[1][c] + d * u[2][r] * v[2][c]);
-}
-
-__device__ __forceinline__ float det3f(const float* m) {
-    return m[0] * (m[4] * m[8] - m[7] * m[5]) - m[3] * (m[1] * m[8] - m[7] * m[2]) + m[6] * (m[1] * m[5] - m[4] * m[2]);
-}
-
-__device__ __forceinline__ bool rot_inlier(const float* R, const float* a, const float* q, float cmin) {
-    float r0 = (R[0] * a[0] + R[1] * a[1]) + R[2] * a[2];
-    float r1 = (R[3] * a[0] + R[4] * a[1]) + R[5] * a[2];
-    float r2 = (R[6] * a[0] + R[7] * a[1]) + R[8] * a[2];
-    float c = (r0 * q[0] + r1 * q[1]) + r2 * q[2];
-    c = c < -1.f ? -1.f : (c > 1.f ? 1.f : c);
-    return c >= cmin;  // (float)acos((double)c) < thr (ransac_cos_bound)
-}
-
-// one wavefront per hypothesis: count[it] = inliers, or -1 when |det R - 1| > 0.1 (skipped)
-__global__ void __launch_bounds__(256) ransac_hyp_kernel(RansacArgs R) {
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int it = blockIdx.x * 4 + wid;
-    if (it >= R.iters) return;
-    const int n = *R.n_good;
-    if (n < 3) return;
-#ifdef TRK_STAMPS
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
-    float Hm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int s = 0; s < 3; ++s) {
-        int k = R.samples[3 * it + s];
-        const float* q = R.b1 + 3 * k;
-        const float* a = R.b0 + 3 * k;
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) Hm[3 * r + c] += q[r] * a[c];
-    }
-    float Rm[9];
-#ifdef TRK_STAMPS
-    const unsigned long long ts1 = __builtin_amdgcn_s_memtime();
-#endif
-    kabsch_rotation(Hm, Rm);
-#ifdef TRK_STAMPS
-    const unsigned long long ts2 = __builtin_amdgcn_s_memtime();
-#endif
-#pragma unroll
-    for (int i = 0; i < 9; ++i)  // ransac_select reads the best one back
-        if (lane == i) R.rot[9 * it + i] = Rm[i];
-    if (fabsf(det3f(Rm) - 1.0f) > 0.1f) {
-        if (lane == 0) R.count[it] = -1;
-        return;
-    }
-    int cnt = 0;
-    const float cmin = *R.cmin;
-    for (int i = lane; i < n; i += 64) cnt += rot_inlier(Rm, R.b0 + 3 * i, R.b1 + 3 * i, cmin) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if (lane == 0) R.count[it] = cnt;
-#ifdef TRK_STAMPS
-    if (it == 0 && lane == 0)
-        printf("ransac_hyp: loads %llu kabsch %llu count %llu\n", ts1 - ts0, ts2 - ts1, __builtin_amdgcn_s_memtime() - ts2);
-#endif
-}
-
-// first strictly-best hypothesis (256 threads; its rotation into Rs): returns its index, -1 when none
-__device__ int ransac_best(const RansacArgs& R, int n, int* sbest, int* sidx, float* Rs) {
-    int best = 0, bi = -1;
-    if (n >= 3)
-        for (int it = threadIdx.x; it < R.iters; it += 256) {
-            int c = R.count[it];
-            if (c > best) { best = c; bi = it; }  // strictly greater keeps the earliest of this thread
-        }
-    sbest[threadIdx.x] = best;
-    sidx[threadIdx.x] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            int b2 = sbest[threadIdx.x + s], i2 = sidx[threadIdx.x + s];
-            if (b2 > sbest[threadIdx.x] || (b2 == sbest[threadIdx.x] && b2 > 0 && i2 < sidx[threadIdx.x])) {
-                sbest[threadIdx.x] = b2;
-                sidx[threadIdx.x] = i2;
-            }
-        }
-        __syncthreads();
-    }
-    const int bit = sidx[0];
-    if (threadIdx.x == 0 && blockIdx.x == 0) *R.n_in = n < 3 ? n : sbest[0];
-    if (bit >= 0 && threadIdx.x < 9) Rs[threadIdx.x] = R.rot[9 * bit + threadIdx.x];  // ransac_hyp's rotation
-    __syncthreads();
-    return bit;
-}
-// -> mask over the good points, scattered to the input order
-__global__ void __launch_bounds__(256) ransac_select_kernel(RansacArgs R) {
-    __shared__ int sbest[256], sidx[256];
-    __shared__ float Rs[9];
-    const int n = *R.n_good;
-    const int bit = ransac_best(R, n, sbest, sidx, Rs);
-    for (int j = threadIdx.x; j < n; j += 256) {
-        uint8_t m = 1;
-        if (n >= 3 && bit >= 0) m = rot_inlier(Rs, R.b0 + 3 * j, R.b1 + 3 * j, *R.cmin) ? 1 : 0;
-        R.kept[R.gidx[j]] = m;
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 // GFTT.  Tile = 64 x 8 outputs.  Source tile with a halo of H_ (2 for the eig map, 3 when the
@@ -1136,14 +46,6 @@ __device__ __forceinline__ bool gf_masked_in(const GfArgs& G, int x, int y) {
         if ((wbits >> (x & 31)) & 1u) return false;
     }
     return true;
-}
-
-__device__ __forceinline__ uint32_t ord_f32(float v) {
-    uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unord_f32(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
 // compute eig for the EW x EH positions starting at (ex0, ey0) into eig[] (LDS)
@@ -1917,74 +819,6 @@ hipError_t launch_gftt_reset(const GfArgs& g, int* scal, hipStream_t st) {
     return hipGetLastError();
 }
 
-// rasterise the discs of CreateFeatureMask (cv::circle filled, LINE_8; half-widths precomputed
-// on the host from OpenCV's midpoint Circle()) into a 1-bit-per-pixel exclusion mask
-// the bits of columns [x0, x1] (inside the frame) of row y
-__device__ __forceinline__ void disc_span(const DiscArgs& D, int y, int x0, int x1) {
-    for (int x = x0; x <= x1;) {
-        int wi = x >> 5;
-        int b0 = x & 31;
-        int b1 = min(31, x1 - (wi << 5));
-        uint32_t m = (b1 - b0 == 31) ? 0xffffffffu : (((1u << (b1 - b0 + 1)) - 1u) << b0);
-        atomicOr(&D.bits[(size_t)y * D.words + wi], m);
-        x = (wi + 1) << 5;
-    }
-}
-template <bool WRAP>
-__device__ __forceinline__ void disc_raster(const DiscArgs& D, int i, int nthreads) {
-    const float fx = D.pts[2 * i], fy = D.pts[2 * i + 1];
-    const int cx = (int)rintf(fx), cy = (int)rintf(fy);  // Point2f -> Point (cvRound)
-    const int r = D.radius;
-    // seam wrap mode: the columns are taken modulo W -- a span that leaves the frame on one side continues on the
-    // other (radius < W / 2: the two parts never meet); a centre further than W outside draws nothing
-    if (WRAP && (cx < -D.W || cx >= 2 * D.W)) return;
-    for (int dy = -r + (int)threadIdx.x; dy <= r; dy += nthreads) {
-        int y = cy + dy;
-        if (y < 0 || y >= D.H) continue;
-        int hwd = D.halfw[dy < 0 ? -dy : dy];
-        if (WRAP) {
-            const int c = cx < 0 ? cx + D.W : (cx >= D.W ? cx - D.W : cx);
-            const int a = c - hwd, b = c + hwd;
-            disc_span(D, y, max(a, 0), min(b, D.W - 1));
-            if (a < 0) disc_span(D, y, max(a + D.W, 0), D.W - 1);
-            if (b >= D.W) disc_span(D, y, 0, min(b - D.W, D.W - 1));
-            continue;
-        }
-        disc_span(D, y, max(cx - hwd, 0), min(cx + hwd, D.W - 1));
-    }
-}
-template <bool WRAP>
-__global__ void __launch_bounds__(128) disc_mask_kernel(DiscArgs D) {
-    const int k = blockIdx.x;
-    if (D.n_pts_dev && k >= *D.n_pts_dev) return;  // null: the grid is exactly the point count
-    if (D.kept && !D.kept[D.src_index ? D.src_index[k] : k]) return;
-    disc_raster<WRAP>(D, D.src_index ? D.src_index[k] : k, 128);
-}
-
-// tracker pipeline: RANSAC's selection and CreateFeatureMask's discs in one launch (one launch fewer on the
-// critical path).  Workgroup j (compacted point j < n_good; the grid covers every input point) finds the best
-// hypothesis itself -- the same reduction in every workgroup -- tests its point, scatters the kept flag and,
-// when kept, rasterises the point's disc (disc_mask_kernel's rows; D.radius <= 0: no discs)
-template <bool WRAP>
-__global__ void __launch_bounds__(256) ransac_select_disc_kernel(RansacArgs R, DiscArgs D) {
-    __shared__ int sbest[256], sidx[256];
-    __shared__ float Rs[9];
-    __shared__ int s_m;
-    const int n = *R.n_good;
-    if ((int)blockIdx.x >= max(n, 1)) return;  // (workgroup 0 always runs: it writes n_in)
-    const int bit = ransac_best(R, n, sbest, sidx, Rs);
-    const int j = blockIdx.x;
-    if (j >= n) return;
-    if (threadIdx.x == 0) {
-        uint8_t m = 1;
-        if (n >= 3 && bit >= 0) m = rot_inlier(Rs, R.b0 + 3 * j, R.b1 + 3 * j, *R.cmin) ? 1 : 0;
-        R.kept[R.gidx[j]] = m;
-        s_m = m;
-    }
-    __syncthreads();
-    if (s_m && D.radius > 0) disc_raster<WRAP>(D, R.gidx[j], 256);
-}
-
 // ------------------------------------------------------------------------------------------
 // GFTT, local-maximum path (no explicit mask).  The candidate test of pass 2 — v > thr after
 // THRESH_TOZERO and v == the 3x3 dilation — is, for v > thr, the same as v >= each of its eight
@@ -2444,113 +1278,6 @@ __global__ void __launch_bounds__(256) gftt_lm_flatten_kernel(GfArgs G) {
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers
-hipError_t launch_pyr_down(const PyrLevelPair& s, const PyrLevelPair& d, int frames, hipStream_t st) {
-    constexpr int by = 8;
-    dim3 g((d.w + PD_BX - 1) / PD_BX, (d.h + by - 1) / by, frames);
-    if (s.x_wrap) hipLaunchKernelGGL((pyr_down_kernel<by, true>), g, dim3(256), 0, st, s, d);
-    else hipLaunchKernelGGL(pyr_down_kernel<by>, g, dim3(256), 0, st, s, d);
-    return hipGetLastError();
-}
-hipError_t launch_lk(const LkArgs& a, hipStream_t st, const LkAux* aux) {
-    LkAux x;
-    std::memset(&x, 0, sizeof x);
-    if (aux) x = *aux;
-    const int n = a.n > 0 ? a.n : 0, blocks = n + (aux ? LK_AUX_BLOCKS : 0);
-    if (blocks == 0) return hipSuccess;
-    if (a.fb) {
-        const dim3 g(blocks), b(LK_THREADS);
-        if (a.guided != LK_GUESS_NONE) {
-            if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, true, true>), g, b, 0, st, a, x);
-            else hipLaunchKernelGGL((lk_kernel<false, true, true>), g, b, 0, st, a, x);
-        } else if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, false, true>), g, b, 0, st, a, x);
-        else hipLaunchKernelGGL((lk_kernel<false, false, true>), g, b, 0, st, a, x);
-    } else if (a.guided != LK_GUESS_NONE) {
-        if (a.x_wrap) hipLaunchKernelGGL((lk_kernel<true, true>), dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
-        else hipLaunchKernelGGL((lk_kernel<false, true>), dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
-    } else if (a.x_wrap) hipLaunchKernelGGL(lk_kernel<true>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
-    else hipLaunchKernelGGL(lk_kernel<false>, dim3(blocks), dim3(LK_THREADS), 0, st, a, x);
-    return hipGetLastError();
-}
-size_t ransac_raw_words() { return RS_RAW; }
-hipError_t launch_ransac_raw(uint32_t seed, uint32_t* raw, hipStream_t st) {
-    hipLaunchKernelGGL(ransac_raw_kernel, dim3(1), dim3(RS_THREADS), 0, st, seed, raw);
-    return hipGetLastError();
-}
-hipError_t launch_ransac(const RansacArgs& r, bool gen_samples, hipStream_t st) {
-    // with samples to draw: the compaction and the sampler in one 4-wave workgroup (a 16-wave one waits
-    // longer for a CU while GFTT pass 1 fills the chip from the side stream)
-    if (gen_samples)
-        hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
-    else
-        hipLaunchKernelGGL(ransac_prep_kernel, dim3(1), dim3(RP_THREADS), 0, st, r);
-    if (r.iters > 0) hipLaunchKernelGGL(ransac_hyp_kernel, dim3((r.iters + 3) / 4), dim3(256), 0, st, r);
-    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(256), 0, st, r);
-    return hipGetLastError();
-}
-hipError_t launch_ransac_parts(const RansacArgs& r, bool stream, bool rot, hipStream_t st) {
-    if (!stream) hipLaunchKernelGGL(ransac_prep_kernel, dim3(1), dim3(RP_THREADS), 0, st, r);
-    else if (r.x_wrap) hipLaunchKernelGGL((ransac_sample_kernel<true, true>), dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
-    else hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
-    if (rot) {
-        if (r.iters > 0) hipLaunchKernelGGL(ransac_hyp_kernel, dim3((r.iters + 3) / 4), dim3(256), 0, st, r);
-        hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(256), 0, st, r);
-    }
-    return hipGetLastError();
-}
-hipError_t launch_ransac_pipeline(const RansacArgs& r, const DiscArgs& d, hipStream_t st) {
-    if (r.x_wrap) hipLaunchKernelGGL((ransac_sample_kernel<true, true>), dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
-    else hipLaunchKernelGGL(ransac_sample_kernel<true>, dim3(1), dim3(RS_SAMPLE_THREADS), 0, st, r);
-    if (r.iters > 0) hipLaunchKernelGGL(ransac_hyp_kernel, dim3((r.iters + 3) / 4), dim3(256), 0, st, r);
-    if (d.x_wrap) hipLaunchKernelGGL(ransac_select_disc_kernel<true>, dim3(r.n > 0 ? r.n : 1), dim3(256), 0, st, r, d);
-    else hipLaunchKernelGGL(ransac_select_disc_kernel<false>, dim3(r.n > 0 ? r.n : 1), dim3(256), 0, st, r, d);
-    return hipGetLastError();
-}
-hipError_t launch_disc_mask(const DiscArgs& d, int max_pts, hipStream_t st) {
-    if (max_pts <= 0) return hipSuccess;
-    if (d.x_wrap) hipLaunchKernelGGL(disc_mask_kernel<true>, dim3(max_pts), dim3(128), 0, st, d);
-    else hipLaunchKernelGGL(disc_mask_kernel<false>, dim3(max_pts), dim3(128), 0, st, d);
-    return hipGetLastError();
-}
-hipError_t launch_gftt_eig(const GfArgs& g, hipStream_t st) {
-    dim3 grd((g.W + GF_BX - 1) / GF_BX, (g.H + GF_BY * GF_SUB - 1) / (GF_BY * GF_SUB));
-    hipLaunchKernelGGL(gftt_eig_kernel, grd, dim3(256), 0, st, g);
-    return hipGetLastError();
-}
-// after the map (launch_gftt_eig, on this stream or joined into it): masked max, then candidates
-static hipError_t gftt_candidates(const GfArgs& g, hipStream_t st) {
-    dim3 grd((g.W + GF_BX - 1) / GF_BX, (g.H + GF_BY * GF_SUB - 1) / (GF_BY * GF_SUB));
-    hipLaunchKernelGGL(gftt_max_kernel, dim3(GM_BLOCKS), dim3(256), 0, st, g);
-    hipLaunchKernelGGL(gftt_cand_kernel, grd, dim3(256), 0, st, g);
-    return hipGetLastError();
-}
-static size_t gftt_select_lds(const GfArgs& g, bool hash) {
-    const size_t ncell = (size_t)g.gw * g.gh;
-    return (g.grid_global ? 0 : ncell * GS_SLOTS * sizeof(uint32_t)) + (hash ? ncell * sizeof(int) : 0);
-}
-// greedy selection over n_keys sorted keys: the cell-chained variant when its chain heads fit next to
-// the grid in LDS, else the all-pairs walks
-static hipError_t launch_select(const GfArgs& g, const unsigned long long* keys, const unsigned int* n_keys,
-                                unsigned int cap, int fast, hipStream_t st) {
-    const bool hash = gftt_select_lds(g, true) <= GF_SELECT_LDS_MAX;
-    const size_t lds = gftt_select_lds(g, hash);
-    if (g.x_wrap) {  // seam wrap mode
-        if (g.grid_global) {
-            if (hash) hipLaunchKernelGGL((gftt_select_kernel<true, true, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-            else hipLaunchKernelGGL((gftt_select_kernel<true, false, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-        } else {
-            if (hash) hipLaunchKernelGGL((gftt_select_kernel<false, true, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-            else hipLaunchKernelGGL((gftt_select_kernel<false, false, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-        }
-    } else if (g.grid_global) {
-        if (hash) hipLaunchKernelGGL((gftt_select_kernel<true, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-        else hipLaunchKernelGGL((gftt_select_kernel<true, false>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-    } else {
-        if (hash) hipLaunchKernelGGL((gftt_select_kernel<false, true>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-        else hipLaunchKernelGGL((gftt_select_kernel<false, false>), dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
-    }
-    return hipGetLastError();
-}
 // Descending sort of the top-K buffer (n = min(n_top, topk_cap) keys) by rank: the keys are unique
 // (response bits << 32 | pixel address), so key i belongs at position #{keys > key i} -- the order
 // a descending radix sort of the buffer gives.  64 keys per workgroup (one per lane); each of the 16
@@ -2624,34 +1351,71 @@ __global__ void __launch_bounds__(64 * TS_WAVES) gftt_topk_sort_kernel(GfArgs G)
     }
     signal();
 }
-static hipError_t gftt_sort_topk(const GfArgs& g, void*, size_t, hipStream_t st) {
+
+// ------------------------------------------------------------------------------------------
+// launchers
+hipError_t launch_gftt_eig(const GfArgs& g, hipStream_t st) {
+    dim3 grd((g.W + GF_BX - 1) / GF_BX, (g.H + GF_BY * GF_SUB - 1) / (GF_BY * GF_SUB));
+    hipLaunchKernelGGL(gftt_eig_kernel, grd, dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+// after the map (launch_gftt_eig, on this stream or joined into it): masked max, then candidates
+static hipError_t gftt_candidates(const GfArgs& g, hipStream_t st) {
+    dim3 grd((g.W + GF_BX - 1) / GF_BX, (g.H + GF_BY * GF_SUB - 1) / (GF_BY * GF_SUB));
+    hipLaunchKernelGGL(gftt_max_kernel, dim3(GM_BLOCKS), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(gftt_cand_kernel, grd, dim3(256), 0, st, g);
+    return hipGetLastError();
+}
+static size_t gftt_select_lds(const GfArgs& g, bool hash) {
+    const size_t ncell = (size_t)g.gw * g.gh;
+    return (g.grid_global ? 0 : ncell * GS_SLOTS * sizeof(uint32_t)) + (hash ? ncell * sizeof(int) : 0);
+}
+// every instance of gftt_select_kernel, [grid_global][hash][x_wrap]: launch_select picks one, gftt_select_set_lds
+// raises the dynamic-LDS limit of all of them
+using GfSelectKernel = void (*)(GfArgs, const unsigned long long*, const unsigned int*, unsigned int, int);
+static const GfSelectKernel gf_select_kernels[2][2][2] = {
+    {{gftt_select_kernel<false, false, false>, gftt_select_kernel<false, false, true>},
+     {gftt_select_kernel<false, true, false>, gftt_select_kernel<false, true, true>}},
+    {{gftt_select_kernel<true, false, false>, gftt_select_kernel<true, false, true>},
+     {gftt_select_kernel<true, true, false>, gftt_select_kernel<true, true, true>}}};
+// greedy selection over n_keys sorted keys: the cell-chained variant when its chain heads fit next to
+// the grid in LDS, else the all-pairs walks
+static hipError_t launch_select(const GfArgs& g, const unsigned long long* keys, const unsigned int* n_keys,
+                                unsigned int cap, int fast, hipStream_t st) {
+    const bool hash = gftt_select_lds(g, true) <= GF_SELECT_LDS_MAX;
+    const size_t lds = gftt_select_lds(g, hash);
+    const GfSelectKernel k = gf_select_kernels[g.grid_global != nullptr][hash][g.x_wrap != 0];
+    hipLaunchKernelGGL(k, dim3(1), dim3(GS_THREADS), lds, st, g, keys, n_keys, cap, fast);
+    return hipGetLastError();
+}
+static hipError_t gftt_sort_topk(const GfArgs& g, hipStream_t st) {
     hipLaunchKernelGGL(gftt_topk_sort_kernel<16>, dim3((g.topk_cap + 63) / 64), dim3(64 * 16), 0, st, g);
     return hipGetLastError();
 }
 // fast path: candidates -> histogram -> top-K compaction -> sort of the top-K keys -> greedy
-hipError_t launch_gftt(const GfArgs& g, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st) {
+hipError_t launch_gftt(const GfArgs& g, hipStream_t st) {
     hipError_t e = gftt_candidates(g, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gftt_hist_kernel, dim3(256), dim3(256), 0, st, g);
     hipLaunchKernelGGL(gftt_topk_compact_kernel, dim3(256), dim3(256), 0, st, g);
-    e = gftt_sort_topk(g, sort_tmp, sort_tmp_bytes, st);
+    e = gftt_sort_topk(g, st);
     if (e != hipSuccess) return e;
     return launch_select(g, (const unsigned long long*)g.topk_sorted, (const unsigned int*)g.n_top, g.topk_cap, 1, st);
 }
 hipError_t launch_gftt_lmax(const GfArgs& g, hipStream_t st) {
-    if (g.static_bits) hipLaunchKernelGGL(gftt_lmax_kernel<true>, dim3(g.tiles_x * g.tiles_y), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(gftt_lmax_kernel<false>, dim3(g.tiles_x * g.tiles_y), dim3(256), 0, st, g);
+    const auto k = g.static_bits ? gftt_lmax_kernel<true> : gftt_lmax_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(g.tiles_x * g.tiles_y), dim3(256), 0, st, g);
     return hipGetLastError();
 }
 // after pass 1 and the disc mask: masked maximum (clean tiles, then the touched tiles that could
 // raise it), candidate histogram, cut, top-K, sort, greedy selection
-hipError_t launch_gftt_after_lmax(const GfArgs& g, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st) {
+hipError_t launch_gftt_after_lmax(const GfArgs& g, hipStream_t st) {
     const int n_tiles = g.tiles_x * g.tiles_y;
     hipLaunchKernelGGL(gftt_tmax_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, st, g);
     hipLaunchKernelGGL(gftt_dirty_kernel, dim3(n_tiles * (LM_TY / LM_STRIP)), dim3(256), 0, st, g);
     hipLaunchKernelGGL(gftt_lm_hist_kernel, dim3(256), dim3(256), 0, st, g);
     hipLaunchKernelGGL(gftt_lm_topk_kernel, dim3(256), dim3(256), 0, st, g);
-    hipError_t e = gftt_sort_topk(g, sort_tmp, sort_tmp_bytes, st);
+    hipError_t e = gftt_sort_topk(g, st);
     if (e != hipSuccess) return e;
     return launch_select(g, (const unsigned long long*)g.topk_sorted, (const unsigned int*)g.n_top, g.topk_cap, 1, st);
 }
@@ -2700,16 +1464,13 @@ hipError_t gftt_select_set_lds(size_t bytes) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (bytes <= cur[dev]) return hipSuccess;
-    const void* fns[8] = {(const void*)gftt_select_kernel<false, false>, (const void*)gftt_select_kernel<false, true>,
-                          (const void*)gftt_select_kernel<true, false>, (const void*)gftt_select_kernel<true, true>,
-                          (const void*)gftt_select_kernel<false, false, true>,
-                          (const void*)gftt_select_kernel<false, true, true>,
-                          (const void*)gftt_select_kernel<true, false, true>,
-                          (const void*)gftt_select_kernel<true, true, true>};
-    for (const void* f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
+    for (const auto& by_hash : gf_select_kernels)
+        for (const auto& by_wrap : by_hash)
+            for (const GfSelectKernel f : by_wrap) {
+                const hipError_t e =
+                    hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+                if (e != hipSuccess) return e;
+            }
     cur[dev] = bytes;
     return hipSuccess;
 }

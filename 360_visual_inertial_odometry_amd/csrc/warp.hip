@@ -8,8 +8,8 @@
 // in numpy by tests/warp_oracle.py, which this kernel matches bitwise.
 //
 // One lane per destination pixel; the grid is (256-column tile, row) in launch order (giving each XCD a contiguous
-// range of blocks, as tracker.hip does, measured 5 to 30 % slower: DESIGN 4.7).  A lane's map entry (quantised on
-// the host, WarpEntry) is one aligned 8-byte load and stays in registers while the lane loops over the frames of
+// range of blocks, as trk_lk.hip and trk_gftt.hip do, measured 5 to 30 % slower: DESIGN 4.7).  A lane's map entry
+// (quantised on the host, WarpEntry) is one aligned 8-byte load and stays in registers while the lane loops over the frames of
 // the launch, so the map is read once per launch.  The taps are loaded from addresses clamped into the source
 // frame, whatever the border modes, and a tap that the modes put outside the frame is replaced by border_value
 // afterwards: nothing outside [0, sW bpp) of a source row or outside rows [0, sH) is ever read.  No LDS, no scratch.

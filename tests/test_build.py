@@ -46,10 +46,11 @@ def built(vio):
     ("vio360.h", {"ba_kernel", "ba_host", "ba_global", "ba_global_host", "tracker_host", "frontend_host"}),
     ("resize.h", {"resize", "resize_host"}),
     ("frame_io.h", {"resize_host", "warp_host", "equalize_host", "mask_host", "tracker_host"}),
-    ("tracker_types.h", {"tracker", "tracker_host", "frontend_host"}),
+    ("tracker_types.h", {"trk_lk", "trk_ransac", "trk_gftt", "tracker_host", "frontend_host"}),
     # (new rows go last: the generated ids of the rows above carry their position)
     ("ba_launch.h", {"ba_kernel", "ba_cluster", "ba_host", "ba_global_host", "imu_init", "lie_host"}),
     ("ctx.h", {"ctx", "ba_host", "ba_global_host", "tracker_host", "resize_host"}),
+    ("trk_dev.h", {"trk_lk", "trk_ransac", "trk_gftt"}),
 ])
 def test_touching_a_header_rebuilds_its_dependents(built, header, must):
     deps = set(_includers(header))
@@ -60,6 +61,25 @@ def test_touching_a_header_rebuilds_its_dependents(built, header, must):
     dry = _make("-n", "-W", path).stdout
     rebuilt = set(re.findall(r"-o build/(\w+)\.o", dry))
     assert rebuilt == deps, (header, sorted(rebuilt), sorted(deps))
+
+
+def test_strict_units_compile_without_fma_contraction():
+    """every unit named in the Makefile's STRICT list is compiled with -ffp-contract=off, and the three tracker
+    units are among them: a tracker unit built without the flag would only show up as bitwise failures on the GPU"""
+    text = open(os.path.join(CSRC, "Makefile")).read()
+    strict = set(re.search(r"^STRICT\s*:=\s*(.*)$", text, re.M).group(1).split())
+    assert {"trk_lk", "trk_ransac", "trk_gftt"} <= strict, sorted(strict)
+    dry = _make("-n", "-B")
+    assert dry.returncode == 0, dry.stderr
+    lines = {}  # unit -> its compile line
+    for line in dry.stdout.splitlines():
+        m = re.search(r"-c (\w+)\.(?:hip|cpp) -o build/(\w+)\.o", line)
+        if m:
+            assert m.group(1) == m.group(2), line
+            lines[m.group(1)] = line
+    assert strict <= set(lines), sorted(strict - set(lines))
+    missing = sorted(u for u in strict if "-ffp-contract=off" not in lines[u].split())
+    assert not missing, missing
 
 
 def test_translation_units_agree_on_struct_layouts(vio):

@@ -147,7 +147,8 @@ __global__ __launch_bounds__(64) void imu_preint_kernel(ImuArgs a) {
         const int m = (e + hi) >> 1;
         if (a.imu[m].timestamp < iv.t1) e = m + 1; else hi = m;
     }
-    const int cnt = e - lo;
+    // a NaN bound fails both comparisons of the reference's filter (ts >= t0 && ts < t1): empty
+    const int cnt = (iv.t0 == iv.t0 && iv.t1 == iv.t1) ? e - lo : 0;
     vio_preint* o = a.out + i;
     if (cnt <= 0) {  // Preintegrate returns nullptr (:165-169)
         if (q == 0) {

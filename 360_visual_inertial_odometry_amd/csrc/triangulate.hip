@@ -8,7 +8,8 @@
 //   A.row(2) = b2(0)·T2w.row(2) − b2(2)·T2w.row(0)
 //   A.row(3) = b2(1)·T2w.row(2) − b2(2)·T2w.row(1)
 //   v = right singular vector of A for the smallest singular value (JacobiSVD .matrixV().col(3));
-//   invalid if |v(3)| < 1e-10; X = v.head<3>() / v(3); invalid unless finite.
+//   invalid if |v(3)| < 1e-10; X = v.head<3>() / v(3); invalid unless finite.  A non-finite A
+//   (NaN / inf in a bearing or a pose) is invalid here whatever the sweeps leave in v.
 // The reference runs Eigen's f32 two-sided JacobiSVD; here the 4x4 SVD is a one-sided (Hestenes)
 // Jacobi in f64 on the f32-built A (the null vector is unique up to sign, which the division
 // cancels), rounded to f32 at the end.  Also returns the reprojection angle errors in pixels that
@@ -111,9 +112,14 @@ __global__ __launch_bounds__(256) void triangulate_kernel(TriArgs a) {
     // smallest singular value = shortest column; its V column is the null vector
     int kmin = 0;
     double nmin = 0.0;
+    // a NaN / inf in a bearing or a pose stays in its column of A (such a column never passes the
+    // rotation test above), so its squared norm tells: the candidate is invalid, whichever of the
+    // other columns came out shortest
+    bool finite = true;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const double nk = ((col[k][0] * col[k][0] + col[k][1] * col[k][1]) + col[k][2] * col[k][2]) + col[k][3] * col[k][3];
+        finite = finite && nk <= 1.7976931348623157e308;
         if (k == 0 || nk < nmin) {
             nmin = nk;
             kmin = k;
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(256) void triangulate_kernel(TriArgs a) {
     double v[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = kmin == 0 ? V[0][r] : (kmin == 1 ? V[1][r] : (kmin == 2 ? V[2][r] : V[3][r]));
-    bool ok = fabs(v[3]) >= 1e-10;
+    bool ok = finite && fabs(v[3]) >= 1e-10;
     float X[3] = {0.f, 0.f, 0.f};
     if (ok) {
 #pragma unroll

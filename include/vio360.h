@@ -544,7 +544,8 @@ typedef struct {
  * interval i integrates the samples with t_start[i] <= timestamp < t_end[i] under the biases
  * gyro_bias[3i..], accel_bias[3i..] (the preintegrator's m_gyro_bias / m_accel_bias; NULL = 0).
  * imu[] must be sorted by non-decreasing timestamp (VIO_EINVAL otherwise).  valid[i] = 0 where
- * the reference returns nullptr (no sample in range; out[i] is then zeroed).  cov_bias_diag
+ * the reference returns nullptr (no sample in range — a NaN bound keeps none, ±inf bounds compare
+ * as usual; out[i] is then zeroed).  cov_bias_diag
  * (n*6, may be NULL) receives covariance(9..14, 9..14)'s diagonal, the random-walk block.
  * noise NULL = the reference defaults.  Blocking; out / valid / cov_bias_diag are host buffers.
  */
@@ -613,7 +614,8 @@ int vio_imu_init_solve(vio_ctx* ctx, const vio_imu_init_problem* probs, vio_imu_
  * kf->GetTwc().inverse(), Estimator.cpp:1163-1164).  Candidate i triangulates bearings
  * bearings[6i..6i+2] (in camera pose_pair[2i]) and bearings[6i+3..6i+5] (in camera pose_pair[2i+1])
  * (Feature::GetBearing, unit f32).  points: 3n f32; valid[i] = TriangulateSinglePoint's return
- * (|v(3)| >= 1e-10 and a finite point); pixel_err (2n, may be NULL) = the reprojection angle errors
+ * (|v(3)| >= 1e-10 and a finite point; a candidate whose bearings or poses hold a NaN or an inf is
+ * invalid); invalid candidates get point 0 and error 0; pixel_err (2n, may be NULL) = the reprojection angle errors
  * in pixels TriangulateNewMapPoints computes (:1233-1248) with `width` = GetWidth().  Blocking; host
  * buffers.  The 4x4 SVD is an f64 one-sided Jacobi on the f32-built A (reference: Eigen's f32
  * JacobiSVD; the null vector is unique up to sign, which the division cancels).

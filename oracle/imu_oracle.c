@@ -15,7 +15,10 @@
  *     15x15 random-walk update as full dense matrices;
  *   - sin / cos of the rotation angle are the f64 values rounded once to f32 (a correctly rounded
  *     sinf / cosf); sqrt and division are IEEE f32.
- * The oracle is pinned by (tests/test_imu_oracle.py): the independent numpy f32 restatement
+ * The oracle is pinned by the independent float64 reference of tests/imu_preint_reference.py on the
+ * named cases of tests/imu_preint_cases.py (hard motion, long chains, the θ = 1e-6 switch, large
+ * biases, every range rule; tests/test_imu_preint_reference.py, tolerance from the reference's own
+ * f32 floor), and by (tests/test_imu_oracle.py): the numpy f32 restatement
  * (360_visual_inertial_odometry_amd/synth.py:preintegrate, BLAS products) to f32 rounding, the
  * closed forms of constant-rate rotation / constant acceleration (ΔR = Exp(ω·T),
  * ΔV = a·T, ΔP = ½·a·T² for ω = 0), and the reference's range / dt rules (half-open filter,
@@ -189,7 +192,8 @@ int oracle_imu_preintegrate(const vio_imu_data* imu, int n_imu, const double* t_
         /* the filter of :158-163, on sorted input the contiguous range [lo, hi) */
         int lo = lower_bound(imu, 0, n_imu, t_start[i]);
         int hi = lower_bound(imu, lo, n_imu, t_end[i]);
-        if (hi <= lo) {
+        /* a NaN bound fails both comparisons of the filter: nothing is kept */
+        if (hi <= lo || t_start[i] != t_start[i] || t_end[i] != t_end[i]) {
             memset(&out[i], 0, sizeof(out[i]));
             if (cov_bias_diag) memset(cov_bias_diag + 6 * i, 0, 6 * sizeof(float));
             valid[i] = 0;

@@ -48,22 +48,27 @@ def triangulate(T_cw, pairs, bearings, width):
     n = len(pairs)
     T1, T2 = T_cw[pairs[:, 0]], T_cw[pairs[:, 1]]
     b1, b2 = bearings[:, :3], bearings[:, 3:]
-    A = build_A(T1, T2, b1, b2).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        A = build_A(T1, T2, b1, b2).astype(np.float64)
     X = np.zeros((n, 3), F32)
     valid = np.zeros(n, np.uint8)
     err = np.zeros((n, 2), F32)
     if n == 0:
         return X, valid, err
-    _, _, Vt = np.linalg.svd(A)
-    v = Vt[:, 3, :]
-    ok = np.abs(v[:, 3]) >= 1e-10
+    # a NaN / inf in a bearing or a pose: no finite point can come of it (and LAPACK raises on it)
+    fin = np.isfinite(A).all((1, 2))
+    v = np.zeros((n, 4))
+    if fin.any():
+        v[fin] = np.linalg.svd(A[fin])[2][:, 3, :]
+    ok = fin & (np.abs(v[:, 3]) >= 1e-10)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         P = (v[:, :3] / np.where(ok, v[:, 3], 1.0)[:, None]).astype(F32)
     ok &= np.isfinite(P).all(1)
     X[ok] = P[ok]
     valid[ok] = 1
-    e1 = reproj_px(T1, b1, X, width)
-    e2 = reproj_px(T2, b2, X, width)
+    with np.errstate(invalid="ignore", over="ignore"):
+        e1 = reproj_px(T1, b1, X, width)
+        e2 = reproj_px(T2, b2, X, width)
     err[:, 0] = np.where(ok, e1, 0)
     err[:, 1] = np.where(ok, e2, 0)
     return X, valid, err

@@ -3,12 +3,20 @@
 Both evaluate IMUPreintegrator::Preintegrate (src/processing/IMUPreintegrator.cpp:143-274) in f32
 with the same expression order, no FMA contraction and correctly rounded sin / cos, so every f32
 field and dt_total must be identical (compared with ==, so ±0 agree).
+
+The named cases of tests/imu_preint_cases.py (aggressive motion, long chains, the θ = 1e-6 switch
+between neighbouring intervals of one wave, large biases, non-default noise, every range rule with
+NaN / ±inf bounds) run three ways: bitwise against the C oracle through the host entry, through the
+device entry into 0xFF-filled buffers, and directly against the independent f64 reference
+(tests/imu_preint_reference.py) with the tolerance derived in test_imu_preint_reference.py.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import imu_preint_cases
+import imu_preint_reference
 import oracle_lib
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +79,74 @@ def test_edge_cases_bitwise(vio, ctx):
     o = oracle_lib.imu_preintegrate(vio, s, t0, t1)
     np.testing.assert_array_equal(g[1], [1, 1, 1, 0, 0, 0, 0])
     _assert_same(g, o)
+
+
+def _case_runs(vio, synth, ctx, name):
+    """[(part, kernel result, oracle result)] of one named case, through the host entry."""
+    out = []
+    for p in imu_preint_cases.case(name, synth):
+        args = (p["samples"], p["t0"], p["t1"], p["bg"], p["ba"], p["noise"])
+        out.append((p, ctx.imu_preintegrate(*args), oracle_lib.imu_preintegrate(vio, *args)))
+    return out
+
+
+@pytest.mark.parametrize("name", imu_preint_cases.NAMES)
+def test_named_cases_bitwise(vio, synth, ctx, name):
+    """Hard motion, the θ = 1e-6 switch inside one wave, large biases, non-default noise and every
+    range rule (tests/imu_preint_cases.py): kernel == C oracle, bit for bit."""
+    for p, g, o in _case_runs(vio, synth, ctx, name):
+        _assert_same(g, o)
+
+
+@pytest.mark.parametrize("name", imu_preint_cases.NAMES)
+def test_named_cases_against_f64_reference(vio, synth, ctx, name):
+    """The device result against the independent f64 reference directly (not through the C oracle),
+    with the bound of test_imu_preint_reference.py: valid and dt_total exact, every other field
+    within 4·floor + 4·2⁻²⁴·max|field|.  Bitwise parity with the oracle makes the measured
+    error / bound ratios those of that module's table."""
+    got = [g for _, g, _ in _case_runs(vio, synth, ctx, name)]
+    r64 = imu_preint_cases.reference(name, synth, "f64")
+    rat = imu_preint_cases.ratios(got, name, synth)
+    print(name, " ".join(f"{k}={max((float(d[k].max()) for d in rat if len(d[k])), default=0.0):.3f}"
+                         for k in imu_preint_reference.FIELDS))
+    for pi, ((rec, valid, _), r, d) in enumerate(zip(got, r64, rat)):
+        assert np.array_equal(valid, r["valid"]), (name, pi, valid.tolist(), r["valid"].tolist())
+        assert np.array_equal(rec["dt_total"], r["dt_total"]), (name, pi)
+        for k in imu_preint_reference.FIELDS:
+            assert (d[k] <= 1.0).all(), (name, pi, k, int(d[k].argmax()), float(d[k].max()))
+
+
+@pytest.mark.parametrize("name", ["aggressive", "threshold", "ranges"])
+def test_named_cases_device_entry_into_poisoned_buffers(vio, synth, ctx, name):
+    """vio_imu_preintegrate_device into caller-owned buffers that start as 0xFF bytes: every record,
+    valid flag and bias-walk row of every interval — invalid ones included — must be written, and
+    nothing past the n-th."""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    sz = C.sizeof(vio.abi.VioPreint)
+    for p in imu_preint_cases.case(name, synth):
+        n = len(p["t0"])
+        o = oracle_lib.imu_preintegrate(vio, p["samples"], p["t0"], p["t1"], p["bg"], p["ba"], p["noise"])
+        imu = vio.abi.imu_array(p["samples"])
+        d_imu = torch.from_numpy(imu.view(np.uint8).copy()).to(dev)
+        d_t0, d_t1 = torch.from_numpy(p["t0"]).to(dev), torch.from_numpy(p["t1"]).to(dev)
+        d_bg = None if p["bg"] is None else torch.from_numpy(p["bg"]).to(dev)
+        d_ba = None if p["ba"] is None else torch.from_numpy(p["ba"]).to(dev)
+        d_out = torch.full(((n + 1) * sz,), 0xFF, dtype=torch.uint8, device=dev)
+        d_valid = torch.full((n + 1,), 0xFF, dtype=torch.uint8, device=dev)
+        d_cov = torch.full(((n + 1) * 24,), 0xFF, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        ctx.imu_preintegrate_device(d_imu.data_ptr(), len(imu), d_t0.data_ptr(), d_t1.data_ptr(), n, d_out.data_ptr(),
+                                    d_valid.data_ptr(), d_cov.data_ptr(),
+                                    None if d_bg is None else d_bg.data_ptr(),
+                                    None if d_ba is None else d_ba.data_ptr(), p["noise"])
+        ctx.imu_kernel_ms()  # waits
+        raw, valid, cov = d_out.cpu().numpy(), d_valid.cpu().numpy(), d_cov.cpu().numpy()
+        assert (raw[n * sz:] == 0xFF).all() and valid[n] == 0xFF and (cov[n * 24:] == 0xFF).all()
+        rec = vio.abi.preint_records((vio.abi.VioPreint * n).from_buffer_copy(raw[:n * sz].tobytes()))
+        _assert_same((rec, valid[:n], cov[:n * 24].view(np.float32).reshape(n, 6)), o)
+        pad = raw[:n * sz].reshape(n, sz)[:, vio.abi.VioPreint._pad.offset:vio.abi.VioPreint._pad.offset + 8]
+        assert not pad.any()
 
 
 def test_empty_inputs_and_errors(vio, ctx):

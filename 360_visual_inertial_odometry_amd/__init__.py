@@ -17,7 +17,9 @@ from .abi import (VIO_BA_FULL, VIO_BA_LOCAL, VIO_BA_VI, VIO_PNP, VIO_SEAM_CUT, V
                   default_klt_params, default_tracker_params,
                   VIO_FB_OFF, VIO_FB_ON, VIO_FB_NOT_RUN, VIO_FB_PASS, VIO_FB_BACK_LOST, VIO_FB_TOO_FAR,
                   ErpFbParams, default_fb_params,
-                  VIO_EPI_OFF, VIO_EPI_ON, ErpEpiParams, ErpEpiInfo, default_epi_params)
+                  VIO_EPI_OFF, VIO_EPI_ON, ErpEpiParams, ErpEpiInfo, default_epi_params,
+                  VIO_PNPR_OK, VIO_PNPR_TOO_FEW, VIO_PNPR_NO_MODEL, VIO_PNPR_FEW_INLIERS, VioPnpRansacParams,
+                  VioPnpRansacResult, default_pnp_ransac_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIO360_LIB") or os.path.join(_HERE, "libvio360.so")
@@ -76,6 +78,7 @@ EXPORTS = [
     "vio_ba_gather", "vio_ba_write_back", "vio_imu_init_solve",
     "vio_mono_init_solve", "vio_mono_init_kernel_ms", "vio_mono_init_samples", "vio_init_select_features",
     "vio_init_parallax", "vio_init_compose", "vio_ctx_set_ba_route",
+    "vio_pnp_ransac_check", "vio_pnp_ransac", "vio_pnp_ransac_kernel_ms", "vio_pnp_correspondences", "vio_pnp_compose",
     "vio_window_create", "vio_window_destroy", "vio_window_add_mappoint", "vio_window_add_observation",
     "vio_window_link_mappoints", "vio_window_add_keyframe", "vio_window_triangulation_candidates",
     "vio_window_commit_triangulation", "vio_window_triangulate", "vio_window_keyframes", "vio_window_num_mappoints",
@@ -259,6 +262,15 @@ def lib():
     L.vio_init_parallax.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_float)]
     L.vio_init_compose.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int]
     L.vio_ctx_set_ba_route.argtypes = [vp, C.c_int]
+    if hasattr(L, "vio_pnp_ransac") or "VIO360_LIB" not in os.environ:  # (A/B: older builds)
+        prp = C.POINTER(abi.VioPnpRansacParams)
+        L.vio_pnp_ransac_check.argtypes = [prp, C.c_int, C.c_int]
+        L.vio_pnp_ransac.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, prp, C.POINTER(abi.VioPnpRansacResult),
+                                     vp, vp]
+        L.vio_pnp_ransac_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+        L.vio_pnp_correspondences.argtypes = [C.POINTER(abi.VioMapView), C.c_int, vp, vp, vp, C.c_int,
+                                              C.POINTER(C.c_int)]
+        L.vio_pnp_compose.argtypes = [vp, vp, vp, vp]
     L.vio_window_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.vio_window_destroy.argtypes = [vp]
     L.vio_window_add_mappoint.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
@@ -397,6 +409,29 @@ class Context:
 
     def mono_init_kernel_ms(self):
         return _kernel_ms(self, self.h, "vio_mono_init_kernel_ms")
+
+    # ---- absolute-pose RANSAC on map points ----
+    def pnp_ransac(self, points, bearings, samples, R=None, params=None, want_mask=True, want_counts=True):
+        """vio_pnp_ransac: points (n,3) f32 world, bearings (n,3) f32 unit, samples (iters,3) int32 (ransac_samples).
+        R None: P3P on all three indices of a row; R (3x3, R_cw): the known-rotation two-point solve on the first
+        two.  -> (result dict, mask (n,) u8 or None, counts (iters,) int32 or None; -1: the row was skipped)."""
+        P = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        B = np.ascontiguousarray(bearings, np.float32).reshape(-1, 3)
+        S = np.ascontiguousarray(samples, np.int32).reshape(-1, 3)
+        n, iters = len(P), len(S)
+        prm = params if params is not None else default_pnp_ransac_params()
+        Rf = None if R is None else np.ascontiguousarray(R, np.float32).reshape(9)
+        res = abi.VioPnpRansacResult()
+        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+        counts = np.zeros(max(iters, 1), np.int32) if want_counts else None
+        self.check(lib().vio_pnp_ransac(self.h, _p(P), _p(B), n, _p(Rf) if Rf is not None else None, _p(S), iters,
+                                        C.byref(prm), C.byref(res), _p(mask) if want_mask else None,
+                                        _p(counts) if want_counts else None), "vio_pnp_ransac")
+        return (abi.pnp_ransac_result_dict(res), mask[:n] if want_mask else None,
+                counts[:iters] if want_counts else None)
+
+    def pnp_ransac_kernel_ms(self):
+        return _kernel_ms(self, self.h, "vio_pnp_ransac_kernel_ms")
 
     # ---- IMU preintegration ----
     def imu_preintegrate(self, samples, t_start, t_end, gyro_bias=None, accel_bias=None, noise=None):
@@ -968,6 +1003,32 @@ def init_compose(T_BC, R, t, points=None):
     if rc:
         raise VioError(f"vio_init_compose failed ({rc})")
     return T1, T2, X
+
+
+def pnp_correspondences(view, frame=0):
+    """vio_pnp_correspondences (host): the 3D-2D pairs of a frame of an abi.MapView, in the order of
+    ba_gather(view, VIO_PNP).  -> (points (n,3) f32, bearings (n,3) f32, feat (n,) int32)."""
+    cap = int(view.feat_begin[-1]) if len(view.feat_begin) else 0
+    P = np.zeros((max(cap, 1), 3), np.float32)
+    B = np.zeros((max(cap, 1), 3), np.float32)
+    F = np.zeros(max(cap, 1), np.int32)
+    n = C.c_int()
+    rc = lib().vio_pnp_correspondences(C.byref(view.c), int(frame), _p(P), _p(B), _p(F), cap, C.byref(n))
+    if rc:
+        raise VioError(f"vio_pnp_correspondences failed ({rc})")
+    return P[:n.value], B[:n.value], F[:n.value]
+
+
+def pnp_compose(R_cw, t_cw, T_cb):
+    """vio_pnp_compose (host): T_wb = T_cw^-1 T_cb as a (4,4) f32, the VIO_PNP solve's T_wb_init."""
+    R = np.ascontiguousarray(R_cw, np.float64).reshape(9)
+    t = np.ascontiguousarray(t_cw, np.float64).reshape(3)
+    T = np.ascontiguousarray(T_cb, np.float32).reshape(16)
+    out = np.zeros((4, 4), np.float32)
+    rc = lib().vio_pnp_compose(_p(R), _p(t), _p(T), _p(out))
+    if rc:
+        raise VioError(f"vio_pnp_compose failed ({rc})")
+    return out
 
 
 def ransac_samples(seed, n, iters=1000):

@@ -655,6 +655,41 @@ def mono_init_result_dict(r):
 
 
 # ---------------------------------------------------------------------------------------------
+# Absolute-pose RANSAC on map points (vio_pnp_ransac)
+VIO_PNPR_OK, VIO_PNPR_TOO_FEW, VIO_PNPR_NO_MODEL, VIO_PNPR_FEW_INLIERS = range(4)
+
+
+class VioPnpRansacParams(C.Structure):
+    _fields_ = [("inlier_thresh_rad", C.c_float), ("min_pair_angle_rad", C.c_float), ("min_inliers", C.c_int32),
+                ("refit_iters", C.c_int32)]
+
+
+class VioPnpRansacResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("best_hypothesis", C.c_int32), ("best_solution", C.c_int32),
+        ("num_inliers_sample", C.c_int32), ("num_inliers", C.c_int32), ("refit_kept", C.c_int32),
+        ("R_cw", C.c_double * 9), ("t_cw", C.c_double * 3), ("R0_cw", C.c_double * 9), ("t0_cw", C.c_double * 3),
+        ("rms_angle_rad", C.c_double),
+    ]
+
+
+def default_pnp_ransac_params():
+    """0.5 deg inlier angle, sampled bearings at least 1 deg apart, SolvePnP's own gate of 10 inliers, 5 refit
+    iterations"""
+    return VioPnpRansacParams(_deg(0.5), _deg(1.0), 10, 5)
+
+
+def pnp_ransac_result_dict(r):
+    return {
+        "status": r.status, "best_hypothesis": r.best_hypothesis, "best_solution": r.best_solution,
+        "num_inliers_sample": r.num_inliers_sample, "num_inliers": r.num_inliers, "refit_kept": r.refit_kept,
+        "R_cw": np.array(r.R_cw, np.float64).reshape(3, 3), "t_cw": np.array(r.t_cw, np.float64),
+        "R0_cw": np.array(r.R0_cw, np.float64).reshape(3, 3), "t0_cw": np.array(r.t0_cw, np.float64),
+        "rms_angle_rad": r.rms_angle_rad,
+    }
+
+
+# ---------------------------------------------------------------------------------------------
 # Estimator window bookkeeping (vio_window_*; Estimator::CreateKeyframe / TriangulateNewMapPoints)
 _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)

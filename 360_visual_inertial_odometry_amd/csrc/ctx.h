@@ -9,7 +9,7 @@
 
 // first event of each module's timing in vio_ctx::ev: start / end of its last launch (equalisation: start /
 // histograms done / LUTs done / end)
-enum { kEvImu = 0, kEvTri = 2, kEvResize = 4, kEvInit = 6, kEvEq = 8, kEvMask = 12, kEvCount = 14 };
+enum { kEvImu = 0, kEvTri = 2, kEvResize = 4, kEvInit = 6, kEvEq = 8, kEvMask = 12, kEvPnp = 14, kEvCount = 16 };
 
 // Device scratch slots of vio_ctx::bufs (ctx_buffer), one owner each.
 enum {
@@ -41,6 +41,8 @@ enum {
     // the region-mask builds (mask_host.cpp): the uploaded host mask, the two intermediate planes, the
     // footprint tables, the 0 / 255 image of the host entry points
     kSlotMaskSrc, kSlotMaskTmp0, kSlotMaskTmp1, kSlotMaskTab, kSlotMaskDst,
+    // vio_pnp_ransac's arena: inputs, the rows' poses and counts, the result record and the mask
+    kSlotPnpRansac,
     kSlotCount
 };
 // Pinned host slots of vio_ctx::hbufs (ctx_host_buffer): the one-shot window solves' input image, every BA

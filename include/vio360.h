@@ -1223,6 +1223,95 @@ int vio_init_compose(const float* T_BC, const float* R, const float* t, float* T
 
 
 /* ------------------------------------------------------------------------------------------ */
+/* Absolute-pose RANSAC on map points (beyond the reference).  Optimizer::SolvePnP  */
+/* (Optimizer.cpp:83-302, here VIO_PNP) refines the predicted pose and tags outliers around it;  */
+/* a prediction outside its basin, or many wrong map-point links, get no answer.  This stage is  */
+/* the hypothesise-and-verify step before it: minimal poses from sampled 3D-2D pairs, scored by  */
+/* the angle between each bearing and R p + t.  Nothing calls it by itself.  The rule, f64 on    */
+/* the f32 inputs, no contraction, sums in the written order:
+     inputs     n world points p[k] (MapPoint::GetPosition) and bearings b[k] (Feature::GetBearing, unit to f32
+                rounding), iters sample rows (i, j, k) (erp_ransac_samples), the parameters below, and in mode B a
+                rotation R_known.  Formed once on the host in double: c2 = cos^2(inlier_thresh_rad),
+                cp2 = cos^2(min_pair_angle_rad).
+     inlier     x = R p + t (each row ((R0*p0 + R1*p1) + R2*p2) + t), d = b.x:  d > 0 && d*d >= c2 * (x.x).  A
+                non-finite point or bearing is never an inlier.
+     skipped    a row gets count -1 when, over the indices it reads (three in mode A, the first two in mode B),
+                  an index repeats, or a sampled point or bearing has a non-finite component or a zero bearing; or
+                  two sampled bearings are close: e = bi.bj, e > 0 && e*e >= cp2 * ((bi.bi) * (bj.bj)); or
+                  (mode A) the world points are coincident or collinear: with e1 = p2 - p1, e2 = p3 - p1,
+                  c = e1 x e2, c.c > 1e-10 * ((e1.e1) * (e2.e2)) does not hold; or
+                  the solver has no real solution with positive depths (below).
+     mode A     R_known == NULL, P3P.  With y = b / |b|, a12 = |p1 - p2|^2 (a13, a23 alike) and b12 = y1.y2 (b13,
+                b23 alike) the depths l satisfy l1^2 + l2^2 - 2 b12 l1 l2 = a12 and its two siblings.  The solver
+                takes one real root gamma of det(D1 + gamma D2) = 0 (D1 = a23 M12 - a12 M23, D2 = a23 M13 - a13 M23,
+                M the constraints' quadratic forms; 40 Newton steps from outside the cubic's stationary points),
+                splits the degenerate conic D1 + gamma D2 into its two lines in (l1 : l2 : l3) by the adjugate
+                method, cuts each line with D2 (|gamma| < 1) or D1, scales by the sum of the three constraints,
+                polishes each candidate with 5 Gauss-Newton steps on the three constraints, and keeps the
+                candidates whose depths are finite and positive: up to four, in that order (first line's roots,
+                then the second's).  No real line pair, a negative discriminant or no positive candidate: no
+                solution.  Pose of a candidate: R = Y X^-1 with X = [p1-p2, p2-p3, (p1-p2) x (p2-p3)] and Y the same
+                of the scaled bearings l y; t = l1 y1 - R p1.  The row's count is the largest of its poses' counts,
+                best_solution the first pose with that count.  Only + - * / and sqrt are used.
+     mode B     R_known given (it must pass erp_tracker_set_rotation's test, else VIO_EINVAL).  a = R_known p,
+                (I - y y^T)(a + t) = 0 for the row's first two points: N t = -sum (I - y y^T) a with
+                N = sum (I - y y^T), solved by the adjugate; no solution when det N > 0 does not hold, t is not
+                finite, or y.(a + t) > 0 fails for either point.  One pose per row, R0 = R_known.
+     selection  the first row with the strictly greatest count >= 0.  None: status NO_MODEL, zero pose, empty mask.
+                Its count below min_inliers: FEW_INLIERS, pose and mask still reported.  n < 4 (mode A) or n < 3
+                (mode B) or iters == 0: TOO_FEW, nothing launched, zero pose, empty mask, counts -1.
+     refit      when the winner counts at least 3 inliers: refit_iters Gauss-Newton steps on them (the set is fixed):
+                residual unit(R p + t) - b, x <- x + w x x + v, update R <- Q R, t <- Q t + v with Q the rotation of
+                the quaternion (1, w / 2) normalised.  The 27 sums of J^T J and J^T r: lane l of 128 sums points
+                i = l mod 128 in increasing i, the partials are summed in lane order; 6x6 Cholesky in one lane (a
+                non-positive pivot stops the refit at the previous iterate).  In both modes all six parameters are
+                free.  The refit pose is recounted with the same test and kept when it counts at least as many
+                inliers as the minimal pose (refit_kept = 1); mask, num_inliers and rms_angle_rad (the RMS of
+                atan2(|b x x|, b.x) over the inliers) follow the returned pose.
+   The same inputs give bitwise the same outputs, run to run and across contexts. */
+enum { VIO_PNPR_OK = 0, VIO_PNPR_TOO_FEW = 1, VIO_PNPR_NO_MODEL = 2, VIO_PNPR_FEW_INLIERS = 3 };
+typedef struct vio_pnp_ransac_params {
+    float inlier_thresh_rad;   /* angle between the bearing and R p + t (0.5 deg) */
+    float min_pair_angle_rad;  /* two sampled bearings must differ by at least this (1 deg) */
+    int32_t min_inliers;       /* below this the status is FEW_INLIERS (10, SolvePnP's own gate) */
+    int32_t refit_iters;       /* Gauss-Newton iterations on the winner's inliers, 0..10 (5) */
+} vio_pnp_ransac_params;
+typedef struct vio_pnp_ransac_result {
+    int32_t status;              /* VIO_PNPR_* */
+    int32_t best_hypothesis;     /* the winning row, -1: none */
+    int32_t best_solution;       /* its pose 0..3, -1: none */
+    int32_t num_inliers_sample;  /* the winning minimal pose's count */
+    int32_t num_inliers;         /* of the returned pose (after the refit when it is kept) */
+    int32_t refit_kept;          /* 1: R_cw / t_cw are the refit, 0: the minimal pose */
+    double R_cw[9], t_cw[3];     /* x_c = R_cw x_w + t_cw, row-major */
+    double R0_cw[9], t0_cw[3];   /* the winning minimal pose */
+    double rms_angle_rad;        /* over the returned pose's inliers */
+} vio_pnp_ransac_result;
+
+/* host only, and the first thing every entry point does: VIO_EINVAL for a null pointer, a NaN or negative field,
+   an angle outside (0, pi/2), refit_iters outside 0..10, n or iters negative or above 4096 */
+int vio_pnp_ransac_check(const vio_pnp_ransac_params* p, int n, int iters);
+/* points [n][3] world, bearings [n][3], R_cw_known 9 floats row-major or NULL, samples [iters][3] with indices
+   < n (mode B reads the first two of a row), mask [n] and counts [iters] may be NULL (-1: skipped).  Blocking. */
+int vio_pnp_ransac(vio_ctx* ctx, const float* points, const float* bearings, int n, const float* R_cw_known,
+                   const int32_t* samples, int iters, const vio_pnp_ransac_params* p, vio_pnp_ransac_result* res,
+                   uint8_t* mask, int32_t* counts);
+/* device time (ms) of the last vio_pnp_ransac's three kernels on this context (waits for them) */
+int vio_pnp_ransac_kernel_ms(vio_ctx* ctx, double* ms);
+/* Host helpers (no device work). */
+/* The 3D-2D pairs of frame `frame` of the view: exactly the observation set and order of
+   vio_ba_gather(map, VIO_PNP, ...) for that frame (valid feature, MapPoint not bad, not near the boundary;
+   the gather itself looks at frame 0).  feat[k] is that gather's obs_feat, points its mp_pos, bearings
+   Camera::PixelToBearing (Camera.cpp:22-47) of feat_uv, evaluated in double and rounded to f32.  Writes at most
+   cap entries; *n is the full count (VIO_EINVAL when it exceeds cap; any output may be NULL with cap 0). */
+int vio_pnp_correspondences(const vio_map_view* map, int frame, float* points, float* bearings, int32_t* feat, int cap,
+                            int* n);
+/* T_wb = T_cw^-1 * T_cb as a row-major f32 4x4 (products in double), ready for vio_ba_problem.T_wb_init of the
+   VIO_PNP solve that follows */
+int vio_pnp_compose(const double R_cw[9], const double t_cw[3], const float T_cb[16], float T_wb[16]);
+
+
+/* ------------------------------------------------------------------------------------------ */
 /* Estimator sliding-window bookkeeping on a host-side keyframe / MapPoint graph:  */
 /* Estimator::CreateKeyframe's observation update and window slide (src/processing/Estimator.cpp: */
 /* 671-754: reference-keyframe transfer, marginalisation, SetBad, RemoveObservation),             */
